@@ -60,3 +60,10 @@ def test_launcher_without_gpus_flag_takes_the_launchers_rank_count():
     # and with no launcher and no flag: one rank
     out = _run(["--steps", "1", "--warmup", "0"], SNERF_BENCH_RANK_CHECK_ONLY="1")
     assert out.returncode == 0 and json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
+
+
+def test_steps_must_be_positive():
+    # --steps is the number of timed steps: zero would leave ms_per_step undefined, so the argument parser refuses it before any work
+    out = _run(["--steps", "0", "--warmup", "0"], HIP_VISIBLE_DEVICES="")
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr, out.stderr[-2000:]
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]

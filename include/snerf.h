@@ -30,7 +30,7 @@ typedef void* snerf_stream_t; /* hipStream_t */
 #define SNERF_ERR_UNSUPPORTED (-2)
 
 #define SNERF_MAX_SCALES 8
-#define SNERF_ABI_VERSION 14
+#define SNERF_ABI_VERSION 15
 
 /* Library identity / diagnostics. */
 int snerf_abi_version(void);
@@ -271,6 +271,30 @@ int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes,
 int snerf_kplanes_density_fwd_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* net);
 int snerf_kplanes_density_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N, const snerf_mlp_desc* net,
                               const float* W, float* density, float* feat, snerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fused proposal density BACKWARD (ABI 15): the mirror of snerf_kplanes_density_fwd for a step that updates the proposal networks.  Per level,
+ * from gdens = d loss / d density it re-gathers the features (bit-identical to the forward's), runs the net's backward (the arithmetic of
+ * snerf_mlp_bwd_ws with aux_col 0 = the trunc_exp derivative: gX bit-identical) and scatters the product rule into grad_planes (the terms of
+ * snerf_kplanes_gather_bwd, run-length combined along longer runs).  Replaces snerf_mlp_bwd_ws + snerf_kplanes_gather_bwd; the forward then
+ * need not write its features.  Up to two levels in ONE launch (disjoint buffers).  ACCUMULATES: grad_planes by float atomics, the net's weight
+ * gradients into `workspace` in the layout of snerf_mlp_bwd_ws (snerf_mlp_gw_workspace_floats floats; fold with snerf_mlp_gw_reduce).
+ * gX (optional, NULL = not written; 16-byte aligned): the [N,8] feature gradient, for tests.  Shapes: snerf_kplanes_density_bwd_supported.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const snerf_kplanes_desc* desc;  /* one scale of six C = 8 planes */
+  const float* planes;
+  const snerf_coords* coords;      /* mode 0 or 1 (mode 1: N a multiple of S) */
+  int64_t N;
+  const snerf_mlp_desc* net;       /* 8 -> 64 -> 1, 16-bit operands */
+  const float* W;
+  const float* gdens;              /* [N] */
+  float* grad_planes;              /* layout of planes */
+  float* workspace;                /* snerf_mlp_bwd_ws layout */
+  float* gX;                       /* [N,8] or NULL */
+} snerf_density_bwd_level;
+int snerf_kplanes_density_bwd_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* net);
+int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, int32_t n_levels, snerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Compositing and ray-level losses (one wavefront per ray, S <= 320).

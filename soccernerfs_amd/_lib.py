@@ -9,7 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libsnerf.so")
 
 MAX_SCALES = 8
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class KPlanesDesc(C.Structure):
@@ -53,6 +53,12 @@ class ResampleArgs(C.Structure):
 class MlpDesc(C.Structure):
     _fields_ = [("d_in", C.c_int32), ("hidden", C.c_int32), ("n_hidden", C.c_int32), ("d_out", C.c_int32),
                 ("hidden_act", C.c_int32), ("out_act", C.c_int32), ("operands", C.c_int32)]
+
+
+class DensityBwdLevel(C.Structure):
+    """snerf_density_bwd_level: one proposal level of snerf_kplanes_density_bwd (pointers to its descriptors and buffers)."""
+    _fields_ = [("desc", C.c_void_p), ("planes", C.c_void_p), ("coords", C.c_void_p), ("N", C.c_int64), ("net", C.c_void_p), ("W", C.c_void_p),
+                ("gdens", C.c_void_p), ("grad_planes", C.c_void_p), ("workspace", C.c_void_p), ("gX", C.c_void_p)]
 
 
 class AdamDyn(C.Structure):
@@ -132,6 +138,7 @@ def lib():
     l.snerf_depth_loss.argtypes = [P, P, P, P, F, I, I, F, P, P, I, P]
     l.snerf_urf_depth_loss.argtypes = [P, P, P, P, P, F, I, I, F, P, P, P, I, P]
     l.snerf_interlevel.argtypes = [P, P, I, P, P, I, I, F, P, P, P]
+    l.snerf_kplanes_density_bwd.argtypes = [P, I, P]
     l.snerf_plane_reg.argtypes = [P, P, P, F, F, F, P, I, I, P]
     l.snerf_adam_step.argtypes = [P, P, P, P, P, L, F, F, F, F, I, F, I, P, P]
     l.snerf_adam_planes_step.argtypes = [P, P, P, P, P, P, F, F, F, P, I, F, F, F, F, I, F, I, P, P]
@@ -261,6 +268,8 @@ EXPORTS = [
     "snerf_kplanes_field_fwd_supported",
     "snerf_kplanes_density_fwd",
     "snerf_kplanes_density_fwd_supported",
+    "snerf_kplanes_density_bwd",
+    "snerf_kplanes_density_bwd_supported",
     "snerf_kplanes_quotient_supported",
     "snerf_kplanes_quotient_prepare",
     "snerf_kplanes_scatter_quotient_scales",

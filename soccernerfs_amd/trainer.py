@@ -119,6 +119,11 @@ class KPlanesTrainConfig:
     # Round 4: each proposal level's density as ONE kernel (csrc/proposal_fused.hip: gather -> 8 -> 64 -> 1 net -> trunc_exp; bit-identical to
     # the two unfused kernels).  The [N,8] features go to HBM only on steps that update the proposal networks.  16-bit operands only.
     fused_proposal: bool = True
+    # Round 7: on steps that update the proposal networks, both levels' net backward + plane scatter as ONE launch (csrc/proposal_bwd.hip:
+    # snerf_kplanes_density_bwd): the features are re-gathered on chip, so the forward does not write them and the [N,8] feature gradient never
+    # crosses HBM.  gX bit-identical to the unfused net backward, plane / weight gradients the same terms in a longer run-length grouping.
+    # Needs fused_proposal (16-bit operands) and the weight-gradient workspaces; never in deterministic mode.  False = the unfused kernels (A-B).
+    fused_proposal_backward: bool = True
     # Round 4: inside train_step (single GPU) pass B of the field scatter is issued on the optimiser sweep's stream, in front of the sweep, instead of
     # on the caller's stream: the caller's stream is then free as soon as the sigma_net backward is queued, so the NEXT step's head (pixel draw, ray
     # generation, proposal levels) runs beside pass B (bound by float atomics) and has mostly finished when the sweep (bound by HBM) starts; and the
@@ -340,6 +345,10 @@ class KPlanesTrainer:
         self.fused_proposal = bool(cfg.fused_proposal and all(self.lib.snerf_kplanes_density_fwd_supported(C.byref(dp), C.byref(net.desc))
                                                              for dp, net in zip(self._desc_prop, self.prop_nets)))
         self._keep_pfeat = True  # train_step clears it for steps that do not update the proposal networks
+        self.fused_proposal_backward = bool(cfg.fused_proposal_backward and self.fused_proposal and not cfg.deterministic
+                                            and all(f"prop{i}.mlp" in self._mlp_ws for i in range(len(self.prop_nets)))
+                                            and all(self.lib.snerf_kplanes_density_bwd_supported(C.byref(dp), C.byref(net.desc))
+                                                    for dp, net in zip(self._desc_prop, self.prop_nets)))
         if self.world > 1:
             self._plan_exchange()
 
@@ -536,7 +545,8 @@ class KPlanesTrainer:
                 with self._span("kplanes_density_fwd"):
                     _lib.check(self.lib.snerf_kplanes_density_fwd(C.byref(self._desc_prop[lvl]), self._p(self.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
                                                                   C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]),
-                                                                  self._p(b["pfeat"][lvl]) if training and self._keep_pfeat else None, self._st),
+                                                                  self._p(b["pfeat"][lvl]) if training and self._keep_pfeat and not self.fused_proposal_backward
+                                                                  else None, self._st),
                                "kplanes_density_fwd")
                 self._resample(lvl, rng["u"][lvl] if training else None, anneal)
             elif lvl < 2:
@@ -785,7 +795,20 @@ class KPlanesTrainer:
                                        b["gdens"][lvl], b["gpfeat"][lvl], cfg.proposal_feature_dim)
         sc = lambda lvl: self._scatter(self._desc_prop[lvl], self.prop_planes[lvl].planes, self._coords[lvl], R * self.S[lvl], b["gpfeat"][lvl],
                                        self.gviews[f"prop{lvl}.planes"])
-        if cfg.interleave_proposal_levels:
+        if self.fused_proposal_backward:
+            # both levels' net backward + plane scatter in one launch (snerf_kplanes_density_bwd), behind the two weights backwards
+            for lvl in (0, 1):
+                wb(lvl)
+            levels = (_lib.DensityBwdLevel * 2)()
+            for lvl in (0, 1):
+                L, net = levels[lvl], self.prop_nets[lvl]
+                L.desc, L.planes, L.coords = C.addressof(self._desc_prop[lvl]), self.prop_planes[lvl].planes.data_ptr(), C.addressof(self._coords[lvl])
+                L.N, L.net, L.W, L.gdens = R * self.S[lvl], C.addressof(net.desc), net.params.data_ptr(), b["gdens"][lvl].data_ptr()
+                L.grad_planes, L.workspace, L.gX = self.gviews[f"prop{lvl}.planes"].data_ptr(), self._mlp_ws[f"prop{lvl}.mlp"].data_ptr(), None
+                self._ws_dirty.add(f"prop{lvl}.mlp")
+            with self._span("kplanes_density_bwd"):
+                _lib.check(self.lib.snerf_kplanes_density_bwd(levels, 2, self._st), "kplanes_density_bwd")
+        elif cfg.interleave_proposal_levels:
             for stage in (wb, nb, sc):
                 for lvl in (0, 1):
                     stage(lvl)

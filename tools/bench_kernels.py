@@ -64,6 +64,44 @@ def main():
         ms_f = timeit(lambda: ops.interpolate_kplanes(pts, pp))
         bytes_f = N * 6 * 4 * 8 * 4
         print(f"prop{lvl} gather: fwd {ms_f:.3f} ms ({bytes_f / ms_f / 1e9:.2f} TB/s alg)")
+    # proposal backward on an updated step, both levels: unfused (per level: snerf_mlp_bwd_ws + snerf_kplanes_gather_bwd from the [N,8] features)
+    # against the fused snerf_kplanes_density_bwd (both levels in one launch, features re-gathered on chip)
+    import ctypes as C
+    from soccernerfs_amd import _lib
+    from soccernerfs_amd.tcnn_compat import Network
+    L = _lib.lib()
+    lv = []
+    for lvl, (S, r) in enumerate(((256, 128), (128, 256))):
+        pp = PlaneSet(8, [[r, r, r, 100]], concat=False, a=0.1, b=0.9, device=dev).requires_grad_(False)
+        net = Network(8, 1, {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 1},
+                      seed=lvl, operands="bf16").to(dev)
+        pts = ray_like_points(R, S, dev, 0.0, 1.0)
+        N = pts.shape[0]
+        d, co = pp.desc(), ops.coords_from_points(pts)
+        feat = ops.interpolate_kplanes(pts, pp).contiguous()
+        gd = torch.randn(N, device=dev) * 1e-3
+        ws = torch.zeros(int(L.snerf_mlp_gw_workspace_floats(C.byref(net.desc))), device=dev)
+        gX, gpl = torch.empty(N, 8, device=dev), torch.zeros_like(pp.planes)
+        lv.append(dict(pp=pp, net=net, pts=pts, N=N, d=d, co=co, feat=feat, gd=gd, ws=ws, gX=gX, gpl=gpl))
+    P = lambda t: C.c_void_p(t.data_ptr())
+
+    def unfused_net(v):
+        _lib.check(L.snerf_mlp_bwd_ws(C.byref(v["net"].desc), P(v["net"].params), P(v["feat"]), 8, C.c_int64(v["N"]), None, 1, 0, P(v["gd"]), P(v["gX"]), 8,
+                                      P(v["ws"]), ops._stream()))
+
+    def unfused_scatter(v):
+        _lib.check(L.snerf_kplanes_gather_bwd(C.byref(v["d"]), P(v["pp"].planes), C.byref(v["co"]), C.c_int64(v["N"]), P(v["gX"]), P(v["gpl"]), ops._stream()))
+
+    arr = (_lib.DensityBwdLevel * 2)()
+    for a, v in zip(arr, lv):
+        a.desc, a.planes, a.coords, a.N = C.addressof(v["d"]), v["pp"].planes.data_ptr(), C.addressof(v["co"]), v["N"]
+        a.net, a.W, a.gdens = C.addressof(v["net"].desc), v["net"].params.data_ptr(), v["gd"].data_ptr()
+        a.grad_planes, a.workspace, a.gX = v["gpl"].data_ptr(), v["ws"].data_ptr(), None
+    t_net = [timeit(lambda v=v: unfused_net(v)) for v in lv]
+    t_sc = [timeit(lambda v=v: unfused_scatter(v)) for v in lv]
+    t_fused = timeit(lambda: _lib.check(L.snerf_kplanes_density_bwd(arr, 2, ops._stream()), "kplanes_density_bwd"))
+    print(f"proposal backward, both levels: unfused {sum(t_net) + sum(t_sc):.3f} ms (net backward {t_net[0]:.3f} + {t_net[1]:.3f}, "
+          f"plane scatter {t_sc[0]:.3f} + {t_sc[1]:.3f}; the forward's [N,8] feature write not counted), fused {t_fused:.3f} ms (one launch)")
     z = torch.zeros(156_000_000, device=dev)
     ms = timeit(lambda: z.zero_())
     print(f"memset 624MB: {ms:.3f} ms ({z.numel() * 4 / ms / 1e9:.2f} TB/s)")

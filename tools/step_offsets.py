@@ -22,11 +22,13 @@ def main():
     ap.add_argument("--interleave-prop-levels", action="store_true")
     ap.add_argument("--sort-before-field-fwd", action="store_true")
     ap.add_argument("--pipeline-sweep", default="off", choices=["coarse_first", "fine_first", "off"])
+    ap.add_argument("--no-fused-proposal-backward", action="store_true", help="unfused net backward + plane scatter per proposal level (A-B)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     R = 4096
-    cfg = KPlanesTrainConfig(interleave_proposal_levels=args.interleave_prop_levels, sort_before_field_fwd=args.sort_before_field_fwd, pipeline_sweep="" if args.pipeline_sweep == "off" else args.pipeline_sweep)
+    cfg = KPlanesTrainConfig(interleave_proposal_levels=args.interleave_prop_levels, sort_before_field_fwd=args.sort_before_field_fwd, pipeline_sweep="" if args.pipeline_sweep == "off" else args.pipeline_sweep,
+                             fused_proposal_backward=not args.no_fused_proposal_backward)
     tr = KPlanesTrainer(cfg, R, dev)
     tr.step = args.start_step
     cams = synthetic.make_cameras(20, 960, 540)

@@ -30,7 +30,7 @@ typedef void* snerf_stream_t; /* hipStream_t */
 #define SNERF_ERR_UNSUPPORTED (-2)
 
 #define SNERF_MAX_SCALES 8
-#define SNERF_ABI_VERSION 15
+#define SNERF_ABI_VERSION 16
 
 /* Library identity / diagnostics. */
 int snerf_abi_version(void);
@@ -260,6 +260,30 @@ int snerf_kplanes_field_fwd_supported(const snerf_kplanes_desc* desc, const sner
 int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
                             const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
                             float* density, float* rgb, void* feat16, float* h, float* feat32, snerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 16: view-dependent colour net of the K-Planes field (KPlanesField with disable_viewing_dependent = False, the reference class's default:
+ * NS/models/kplanes.py:145).  color_net reads X = [SH degree 4 of get_normalized_directions(d) (16) | geometry features h[:, :15] (15)], 31 inputs
+ * (NS/fields/kplanes_field.py:39-44 get_normalized_directions, :206-216 the tcnn SH encoder, :260-262 in_dim_color, :314-323 get_outputs).  The SH
+ * values are those of soccernerfs_amd/sh.py on ((d + 1) / 2) * 2 - 1, bit for bit.
+ *   snerf_kplanes_field_fwd (above) takes the 31 -> 64 -> 64 -> 3 colour net too (snerf_kplanes_field_fwd_supported tells); it then needs
+ *   coords.mode = 1 (per-ray directions) and forms X on chip.  Bit-identical to snerf_kplanes_color_input_fwd + snerf_mlp_fwd with the same operands.
+ *   snerf_kplanes_color_input_fwd: X [N, 32] fp32 = [SH | h[:, :15] | 0] from dirs [N / S, 3] and h [N, 16] (both 16-byte aligned) -- the input
+ *     of the generic MLP kernels (exact fp32 operands, unfused forward, deterministic mode).
+ *   snerf_kplanes_color_input_bwd: gh[:, :15] (row stride 16) = gX[:, 16:31] (row stride ldgx); gh[:, 15] is not written.
+ *   snerf_kplanes_color_bwd_vd(_ws): the colour-net backward with 16-bit operands (wave-owns-rows, csrc/mlp_rows.hip) that forms X itself from
+ *     dirs and h, so no [N, 32] tensor crosses HBM; replaces snerf_kplanes_color_input_fwd + snerf_mlp_bwd(_ws) + snerf_kplanes_color_input_bwd.
+ *     gY = d loss / d rgb [N, ldgy]; gh [N, 16]: columns 0..14 overwritten with the gradient of the geometry features (NULL = not needed);
+ *     weight gradients ACCUMULATED into gW, or into `workspace` in snerf_mlp_bwd_ws's layout (fold with snerf_mlp_gw_reduce).
+ *     _supported: 31 -> 64 -> 64 -> 3, ReLU / Sigmoid, operands bf16 / fp16.
+ * ------------------------------------------------------------------------------------------------ */
+int snerf_kplanes_color_input_fwd(const float* dirs, int32_t S, const float* h, int64_t N, float* X, snerf_stream_t stream);
+int snerf_kplanes_color_input_bwd(const float* gX, int32_t ldgx, int64_t N, float* gh, snerf_stream_t stream);
+int snerf_kplanes_color_bwd_vd_supported(const snerf_mlp_desc* desc);
+int snerf_kplanes_color_bwd_vd(const snerf_mlp_desc* desc, const float* W, const float* dirs, int32_t S, const float* h, int64_t N,
+                               const float* gY, int32_t ldgy, float* gh, float* gW, snerf_stream_t stream);
+int snerf_kplanes_color_bwd_vd_ws(const snerf_mlp_desc* desc, const float* W, const float* dirs, int32_t S, const float* h, int64_t N,
+                                  const float* gY, int32_t ldgy, float* gh, float* workspace, snerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused proposal density = KPlanesDensityField.get_density (NS/fields/kplanes_field.py:410-460) as ProposalNetworkSampler calls it per level

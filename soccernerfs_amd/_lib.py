@@ -9,7 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libsnerf.so")
 
 MAX_SCALES = 8
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class KPlanesDesc(C.Structure):
@@ -266,6 +266,11 @@ EXPORTS = [
     "snerf_urf_depth_loss",
     "snerf_kplanes_field_fwd",
     "snerf_kplanes_field_fwd_supported",
+    "snerf_kplanes_color_input_fwd",
+    "snerf_kplanes_color_input_bwd",
+    "snerf_kplanes_color_bwd_vd",
+    "snerf_kplanes_color_bwd_vd_ws",
+    "snerf_kplanes_color_bwd_vd_supported",
     "snerf_kplanes_density_fwd",
     "snerf_kplanes_density_fwd_supported",
     "snerf_kplanes_density_bwd",

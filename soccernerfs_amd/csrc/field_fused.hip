@@ -23,6 +23,7 @@
 //   sigma 1, colour 0/1/out: small products from LDS-resident weights (21 KB).
 #include "kplanes_common.hpp"
 #include "mlp_lp_common.hpp"
+#include "sh4_common.hpp"
 
 namespace snerf {
 
@@ -38,7 +39,7 @@ struct FieldArgs {
   snerf_coords c;
   int64_t N;
   const float* Wsig;  // [K0 x 128 | 128 x 16] row-major [in][out]
-  const float* Wcol;  // [15 x 64 | 64 x 64 | 64 x 3]
+  const float* Wcol;  // [15 x 64 | 64 x 64 | 64 x 3]; view-dependent: [31 x 64 | 64 x 64 | 64 x 3]
   float* dens;        // [N]   exp(sigma_net(.)[15])
   float* rgb;         // [N,3] sigmoid(color_net(.))
   void* feat16;       // optional [N, 32 n_scales] in the operand type: the rounded feature tile, for an UNFUSED backward (snerf_mlp_bwd_x16)
@@ -53,7 +54,7 @@ struct PlanFF {
   static constexpr int CW0T = SWOT + 16 * LKH;            // colour L0  [64][LKX]
   static constexpr int CW1T = CW0T + FF_HC * LKX;         // colour L1  [64][LKC]
   static constexpr int CWOT = CW1T + FF_HC * LKC;         // colour out [16][LKC]
-  static constexpr int CX = CWOT + 16 * LKC;              // colour input tile [TS][LKX] (columns 15..31 stay zero)
+  static constexpr int CX = CWOT + 16 * LKC;              // colour input tile [TS][LKX] (columns 15..31 stay zero; VD: SH 0..15, h 16..30, 31 zero)
   static constexpr int A1 = CX + FF_TS * LKX;             // sigma hidden tile [TS][LKH]
   static constexpr int XS = A1 + FF_TS * LKH;             // feature tile [TS][LK0]; the colour hidden tiles reuse it once sigma layer 0 is done
   static constexpr int XS_LEN = FF_TS * LK0 > 2 * FF_TS * LKC ? FF_TS * LK0 : 2 * FF_TS * LKC;
@@ -136,7 +137,9 @@ __device__ __forceinline__ void sigma_layer0(const T* XS, const typename Ops<T>:
 
 // KEEP: what a training step leaves behind for its backward -- 0 nothing (eval), 1 the 16-bit feature tile + the sigma_net outputs,
 // 2 those + the fp32 features (quotient scatter).  Compile-time: as run-time pointer tests these cost every variant registers.
-template <typename T, int NS, int KEEP = 0>
+// VD: the view-dependent colour net (kplanes_field.py:206-216, :260-262, :314-323): its input tile holds SH degree 4 of the sample's ray direction
+// (coords mode 1, sh4_common.hpp: the bits of soccernerfs_amd/sh.py) in columns 0..15 and the geometry features in 16..30; layer 0 is 31 x 64.
+template <typename T, int NS, int KEEP = 0, bool VD = false>
 __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, int64_t n_tiles) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -147,14 +150,25 @@ __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, i
   typename Ops<T>::v8 breg[NS];
   load_breg<T, K0>(a.Wsig, wave, lane, breg);
   stage_w<T>(a.Wsig + K0 * FF_H, FF_H, 16, FF_H, 16, nullptr, 0, smem + P::SWOT, P::LKH);
-  stage_w<T>(a.Wcol, FF_GEO, FF_HC, 32, FF_HC, nullptr, 0, smem + P::CW0T, P::LKX);
-  stage_w<T>(a.Wcol + FF_GEO * FF_HC, FF_HC, FF_HC, FF_HC, FF_HC, nullptr, 0, smem + P::CW1T, P::LKC);
-  stage_w<T>(a.Wcol + FF_GEO * FF_HC + FF_HC * FF_HC, FF_HC, 3, FF_HC, 16, nullptr, 0, smem + P::CWOT, P::LKC);
+  constexpr int CIN = VD ? 16 + FF_GEO : FF_GEO, CH0 = VD ? 16 : 0;  // colour-net inputs; first column of the geometry features in CX
+  stage_w<T>(a.Wcol, CIN, FF_HC, 32, FF_HC, nullptr, 0, smem + P::CW0T, P::LKX);
+  stage_w<T>(a.Wcol + CIN * FF_HC, FF_HC, FF_HC, FF_HC, FF_HC, nullptr, 0, smem + P::CW1T, P::LKC);
+  stage_w<T>(a.Wcol + CIN * FF_HC + FF_HC * FF_HC, FF_HC, 3, FF_HC, 16, nullptr, 0, smem + P::CWOT, P::LKC);
   for (int idx = threadIdx.x; idx < FF_TS * P::LKX; idx += blockDim.x) CX[idx] = (T)0.f;  // columns 15..31 stay zero for the whole kernel
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t n0 = tile * FF_TS;
     __syncthreads();  // weights staged / the previous tile's colour layers have read CA1, CA2 (= XS)
     gather_tile<T, NS, KEEP == 2>(a, n0, XS);
+    if constexpr (VD) {  // one SH coefficient per thread: 32 samples x 16 (the previous tile's colour layer 0 read CX before the loop-top barrier)
+      const int sample = threadIdx.x >> 4, k = threadIdx.x & 15;
+      const int64_t n = n0 + sample;
+      float v = 0.f;
+      if (n < a.N) {
+        const int64_t ray = (int64_t)((uint32_t)n / (uint32_t)a.c.S);  // N < 2^31 (validate_field)
+        v = sh4_coeff(k, sh4_kplanes_input(a.c.dirs[ray * 3]), sh4_kplanes_input(a.c.dirs[ray * 3 + 1]), sh4_kplanes_input(a.c.dirs[ray * 3 + 2]));
+      }
+      CX[sample * P::LKX + k] = Ops<T>::cvt(v);
+    }
     __syncthreads();
     if constexpr (KEEP >= 1) {  // the tile's rows are contiguous in feat16: one coalesced 16-B store per 8 features
       T* F16 = reinterpret_cast<T*>(a.feat16);
@@ -176,7 +190,7 @@ __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, i
         if (col == FF_GEO && n < a.N) a.dens[n] = expf(y);  // trunc_exp forward (activations.py:32)
         if constexpr (KEEP >= 1)
           if (n < a.N) a.h[n * 16 + col] = y;
-        CX[(row0 + r) * P::LKX + col] = col < FF_GEO ? Ops<T>::cvt(y) : (T)0.f;
+        CX[(row0 + r) * P::LKX + CH0 + col] = col < FF_GEO ? Ops<T>::cvt(y) : (T)0.f;
       }
     }
     __syncthreads();
@@ -216,17 +230,18 @@ static int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, in
                 max_scales, d->C, d->n_coords, d->concat, d->n_scales);
   SNERF_REQUIRE(sd->d_in == 32 * d->n_scales && sd->hidden == FF_H && sd->n_hidden == 1 && sd->d_out == 16 && sd->hidden_act == 1 && sd->out_act == 0,
                 "kplanes_field: sigma_net must be %d -> 128 (ReLU) -> 16", 32 * d->n_scales);
-  SNERF_REQUIRE(cd->d_in == FF_GEO && cd->hidden == FF_HC && cd->n_hidden == 2 && cd->d_out == 3 && cd->hidden_act == 1 && cd->out_act == 1,
-                "kplanes_field: color_net must be 15 -> 64 -> 64 (ReLU) -> 3 (Sigmoid)");
+  SNERF_REQUIRE((cd->d_in == FF_GEO || cd->d_in == 16 + FF_GEO) && cd->hidden == FF_HC && cd->n_hidden == 2 && cd->d_out == 3 && cd->hidden_act == 1 &&
+                cd->out_act == 1, "kplanes_field: color_net must be 15 -> 64 -> 64 (ReLU) -> 3 (Sigmoid), or 31 -> 64 -> 64 -> 3 (view-dependent)");
   SNERF_REQUIRE((sd->operands == 1 || sd->operands == 2) && cd->operands == sd->operands,
                 "kplanes_field: the fused kernels compute with bf16 / fp16 MFMA operands (operands = 1 / 2, both nets alike); fp32 runs unfused");
   SNERF_REQUIRE(N >= 0 && N < (1LL << 31), "kplanes_field: N=%lld", (long long)N);
   SNERF_REQUIRE(c->mode == 0 || c->mode == 1, "kplanes_field: coords.mode=%d", c->mode);
   if (c->mode == 1) SNERF_REQUIRE(c->S >= 1 && N % c->S == 0, "kplanes_field: N=%lld not a multiple of S=%d", (long long)N, c->S);
+  if (cd->d_in != FF_GEO && N > 0) SNERF_REQUIRE(c->mode == 1, "kplanes_field: the view-dependent colour net reads per-ray directions (coords.mode = 1)");
   return 0;
 }
 
-template <typename T, int NS, int KEEP>
+template <typename T, int NS, int KEEP, bool VD>
 static int launch_field_fwd_k(const FieldArgs& a, hipStream_t st) {
   using P = PlanFF<NS>;
   const int64_t n_tiles = (a.N + FF_TS - 1) / FF_TS;
@@ -234,17 +249,21 @@ static int launch_field_fwd_k(const FieldArgs& a, hipStream_t st) {
   per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // 125 VGPRs: two 8-wave workgroups per CU
   int64_t grid = 256 * per_cu;
   if (grid > n_tiles) grid = n_tiles;
-  auto k = field_fwd_kernel<T, NS, KEEP>;
+  auto k = field_fwd_kernel<T, NS, KEEP, VD>;
   SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, n_tiles);
   SNERF_LAUNCH_CHECK("kplanes_field_fwd");
   return 0;
 }
+template <typename T, int NS, bool VD>
+static int launch_field_fwd_vd(const FieldArgs& a, hipStream_t st) {
+  if (a.feat16 && a.feat32) return launch_field_fwd_k<T, NS, 2, VD>(a, st);
+  if (a.feat16) return launch_field_fwd_k<T, NS, 1, VD>(a, st);
+  return launch_field_fwd_k<T, NS, 0, VD>(a, st);
+}
 template <typename T, int NS>
-static int launch_field_fwd(const FieldArgs& a, hipStream_t st) {
-  if (a.feat16 && a.feat32) return launch_field_fwd_k<T, NS, 2>(a, st);
-  if (a.feat16) return launch_field_fwd_k<T, NS, 1>(a, st);
-  return launch_field_fwd_k<T, NS, 0>(a, st);
+static int launch_field_fwd(const FieldArgs& a, hipStream_t st, bool vd) {
+  return vd ? launch_field_fwd_vd<T, NS, true>(a, st) : launch_field_fwd_vd<T, NS, false>(a, st);
 }
 
 
@@ -280,6 +299,8 @@ using namespace snerf;
 
 extern "C" int snerf_kplanes_field_fwd_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* sigma, const snerf_mlp_desc* color) {
   snerf_coords c = {};
+  c.mode = 1;  // a shape probe: the view-dependent colour net needs per-ray coordinates, which a call then has to pass
+  c.S = 1;
   return desc && sigma && color && validate_field(desc, &c, 0, sigma, color, 6) == 0 ? 1 : 0;
 }
 
@@ -295,5 +316,5 @@ extern "C" int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const flo
   SNERF_REQUIRE((feat16 != nullptr) == (h != nullptr) && (!feat32 || feat16),
                 "kplanes_field_fwd: the training outputs come as a set: feat16 and h together, feat32 only with them");
   a.feat16 = feat16; a.h = h; a.feat32 = feat32;
-  FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, (hipStream_t)stream);
+  FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, (hipStream_t)stream, color->d_in != FF_GEO);
 }

@@ -53,6 +53,9 @@ struct MlpArgs {  // same fields as mlp.hip's (filled there)
   // into replica b % ws_rep instead of gW, so an address collects grid / ws_rep same-address atomics instead of one per workgroup (256 of
   // them took ~25 us at the end of every launch, whatever the element count); snerf_mlp_gw_reduce folds the replicas into gW later.
   float* ws; int ws_rep; int64_t ws_stride;
+  // view-dependent colour backward (snerf_kplanes_color_bwd_vd, mlp_rows.hip): X = [SH4 of the ray direction | h[:, :15]] is formed in the
+  // kernel from the per-ray directions [N / S, 3] and h (X above, row stride ldx = 16)
+  const float* dirs; int S;
 };
 
 __device__ __forceinline__ void gw_add(const MlpArgs& a, int64_t idx, float v) {

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "mlp_rows_common.hpp"
+#include "sh4_common.hpp"
 
 namespace snerf {
 
@@ -59,7 +60,10 @@ struct PlanR {
   static_assert(BYTES <= 160 * 1024, "weights + scratch exceed the CU's LDS");
 };
 
-template <typename T, int K0P, int H, int NH>
+// VD: the view-dependent K-Planes colour net (NS/fields/kplanes_field.py:206-216, :260-262, :314-323): X = [SH4 of the ray direction (16) | h[:, :15] | 0]
+// is formed from a.dirs and h (a.X, ldx 16) in the kernel instead of being read from an [N,32] tensor, and gX is written for the 15 geometry
+// columns only, into gh[:, :15] (a.gX, ldgx 16): the SH columns have no gradient to pass on.
+template <typename T, int K0P, int H, int NH, bool VD = false>
 __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, int64_t n_pairs) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -69,6 +73,7 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
   constexpr float GS = Ops<T>::GS;
   constexpr int NW = P::NW, HB = H / 16, HK = H / 32, KB0 = K0P / 16, KS0 = K0P >= 32 ? K0P / 32 : 1;
   constexpr bool X16K = K0P == 16;  // layer 0 contracts over <= 16 features: one 16x16x16 MFMA per block
+  static_assert(!VD || (K0P == 32 && NH == 2), "the view-dependent colour input is 32 wide, two hidden layers");
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = lane >> 4, c = lane & 15;
 
@@ -161,6 +166,16 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
       const int64_t n = pair * 32 + 16 * sl + c;
       const int64_t nn = n < a.N ? n : nlast;
       const float* xr = a.X + nn * a.ldx;
+      if constexpr (VD) {
+        // lanes g < 2 hold SH coefficients 8g .. 8g+7: their three direction components (scalar loads: rows of 12 bytes); lanes g >= 2 hold
+        // h columns 8(g-2) .. +7.  One pointer per lane, no branch
+        const int64_t ray = a.N < (1LL << 31) ? (int64_t)((uint32_t)nn / (uint32_t)a.S) : nn / a.S;
+        const float* src = g < 2 ? a.dirs + ray * 3 : xr + 8 * (g - 2);
+        const int lim = g < 2 ? 2 : 7;
+        float* xv = &in.xq[sl][0][0].x;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xv[e] = src[e <= lim ? e : lim];
+      } else {
 #pragma unroll
       for (int s = 0; s < KS0; ++s)
 #pragma unroll
@@ -168,9 +183,10 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
           const int f0 = 32 * s + PERL * g + 4 * q;
           in.xq[sl][s][q] = *reinterpret_cast<const float4*>(xr + (f0 <= a.ldx - 4 ? f0 : a.ldx - 4));  // features beyond the row: its last float4 again
         }
-      in.ga[sl] = gap[nn * ga_on];
+      }
+      if constexpr (!VD) in.ga[sl] = gap[nn * ga_on];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < (VD ? 3 : 4); ++r) {  // VD: three outputs (rgb), no aux input
         const int o = 4 * g + r;
         in.gy[sl][r] = gyp[nn * gy_ld + (a.gY && o < a.dout ? o : 0)];
       }
@@ -192,6 +208,14 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
           const float4 t = in.xq[sl][s][q];
           v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
         }
+        if constexpr (VD) {  // SH lanes: the coefficients of their half (sh4_common.hpp: the bits of soccernerfs_amd/sh.py)
+          const float x = sh4_kplanes_input(v[0]), y = sh4_kplanes_input(v[1]), z = sh4_kplanes_input(v[2]);
+          float sh[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) sh[e] = g == 0 ? sh4_coeff(e, x, y, z) : sh4_coeff(8 + e, x, y, z);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = g < 2 ? sh[e] : v[e];
+        }
 #pragma unroll
         for (int e = 0; e < PERL; ++e) v[e] = (live && 32 * s + PERL * g + e < a.d0) ? v[e] : 0.f;
         if constexpr (X16K) {
@@ -203,9 +227,9 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
           x8[sl][s] = bq;
         }
       }
-      gac[sl] = (live && a.gaux) ? in.ga[sl] : 0.f;
+      if constexpr (!VD) gac[sl] = (live && a.gaux) ? in.ga[sl] : 0.f;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) gyc[sl][r] = (live && a.gY && 4 * g + r < a.dout) ? in.gy[sl][r] : 0.f;
+      for (int r = 0; r < 4; ++r) gyc[sl][r] = (live && a.gY && 4 * g + r < (VD ? 3 : a.dout) && (!VD || r < 3)) ? in.gy[sl][VD && r >= 3 ? 0 : r] : 0.f;
     }
   };
 
@@ -299,7 +323,7 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
             gg = gg * sg * (1.f - sg);
           }
           // trunc_exp backward (activations.py:38-39); ga is 0 without gaux.  A select, not a branch: the clamp keeps exp finite for every column
-          gg += o == a.aux_col ? gac[sl] * __expf(fminf(fmaxf(y[sl][r], -15.f), 15.f)) : 0.f;
+          if constexpr (!VD) gg += o == a.aux_col ? gac[sl] * __expf(fminf(fmaxf(y[sl][r], -15.f), 15.f)) : 0.f;
           gv[r] = o < a.dout ? gg * GS : 0.f;
         }
         G0[sl] = v4t{Ops<T>::cvtg(gv[0]), Ops<T>::cvtg(gv[1]), Ops<T>::cvtg(gv[2]), Ops<T>::cvtg(gv[3])};
@@ -380,8 +404,9 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
 
     // ---- gX^T = W0 gZ1^T -> global (lane: features 16 kb + 4g .. +3 of sample c) ----
     if (a.gX) {
+      constexpr int GX_SHIFT = VD ? 16 : 0;  // VD: features 16 .. 30 (h[:, :15]) only, written to gh columns 0 .. 14
 #pragma unroll
-      for (int kb = 0; kb < KB0; ++kb) {
+      for (int kb = GX_SHIFT / 16; kb < KB0; ++kb) {
         const T* wrow = smem + P::W0R + (16 * kb + c) * P::LH + 8 * g;
         f32x4 acc[2] = {};
 #pragma unroll
@@ -394,7 +419,7 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
         for (int sl = 0; sl < 2; ++sl) {
           const int64_t n = pair * 32 + 16 * sl + c;
           const int f0 = 16 * kb + 4 * g;
-          float* dst = a.gX + n * a.ldgx + f0;
+          float* dst = a.gX + n * a.ldgx + f0 - GX_SHIFT;
           const f32x4 o4 = {acc[sl][0] * (1.f / GS), acc[sl][1] * (1.f / GS), acc[sl][2] * (1.f / GS), acc[sl][3] * (1.f / GS)};
           if (n < a.N) {
             if (gvec && f0 + 3 < a.d0) {
@@ -502,7 +527,7 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
   }
 }
 
-template <typename T, int K0P, int H, int NH>
+template <typename T, int K0P, int H, int NH, bool VD = false>
 static int launch_rows(const MlpArgs& a, hipStream_t st) {
   using P = PlanR<K0P, H, NH>;
   static_assert(P::BYTES <= LDS_LIMIT_B, "rows backward does not fit LDS");
@@ -510,7 +535,7 @@ static int launch_rows(const MlpArgs& a, hipStream_t st) {
   int64_t grid = (n_pairs + P::NW - 1) / P::NW;
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
-  auto k = mlp_rows_bwd_kernel<T, K0P, H, NH>;
+  auto k = mlp_rows_bwd_kernel<T, K0P, H, NH, VD>;
   SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(P::NW * 64), P::BYTES, st, a, n_pairs);
   SNERF_LAUNCH_CHECK("mlp_bwd (16-bit operands, wave-owns-rows)");
@@ -538,6 +563,20 @@ int mlp_rows_dispatch(const snerf_mlp_desc* d, const void* args, hipStream_t st)
 #undef CASE
   set_error("mlp rows backward: unsupported shape d_in=%d hidden=%d n_hidden=%d", d->d_in, d->hidden, d->n_hidden);
   return SNERF_ERR_UNSUPPORTED;
+}
+
+// the view-dependent colour net 31 -> 64 -> 64 -> 3 (Sigmoid), 16-bit operands: snerf_kplanes_color_bwd_vd (color_vd.hip)
+bool mlp_rows_vd_supported(const snerf_mlp_desc* d) {
+  return d->d_in == 31 && d->hidden == 64 && d->n_hidden == 2 && d->d_out == 3 && d->hidden_act == 1 && d->out_act == 1 &&
+         (d->operands == 1 || d->operands == 2);
+}
+
+int mlp_rows_vd_dispatch(const snerf_mlp_desc* d, const MlpArgs& a, hipStream_t st) {
+  if (!mlp_rows_vd_supported(d)) {
+    set_error("color_bwd_vd: the kernel is built for 31 -> 64 -> 64 -> 3 (ReLU, Sigmoid) with bf16 / fp16 operands");
+    return SNERF_ERR_UNSUPPORTED;
+  }
+  return d->operands == 2 ? launch_rows<fp16, 32, 64, 2, true>(a, st) : launch_rows<bf16, 32, 64, 2, true>(a, st);
 }
 
 }  // namespace snerf

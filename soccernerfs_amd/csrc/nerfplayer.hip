@@ -5,6 +5,7 @@
 // NS/models/nerfplayer.py:336-341).  The reference runs this as ~10 ATen elementwise / reduction kernels each way.
 // F / 4 lanes per sample, float4 per lane; the three channel reductions of the backward are xor-shuffles inside the lane group.
 #include "common.hpp"
+#include "sh4_common.hpp"
 
 namespace snerf {
 
@@ -71,27 +72,6 @@ __global__ __launch_bounds__(256) void mix_bwd_kernel(const float* __restrict__ 
 // ghx[:, 31:63], added to the camera's row (float atomics, or fixed-point cells).
 // ---------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-__device__ __forceinline__ float sh4_coeff(int k, float x, float y, float z) {
-  const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-  switch (k) {
-    case 0: return 0.28209479177387814f;
-    case 1: return -0.48860251190291987f * y;
-    case 2: return 0.48860251190291987f * z;
-    case 3: return -0.48860251190291987f * x;
-    case 4: return 1.0925484305920792f * xy;
-    case 5: return -1.0925484305920792f * yz;
-    case 6: return 0.94617469575755997f * z2 - 0.31539156525251999f;
-    case 7: return -1.0925484305920792f * xz;
-    case 8: return 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    case 9: return (0.59004358992664352f * y) * (-3.0f * x2 + y2);
-    case 10: return (2.8906114426405538f * xy) * z;
-    case 11: return (0.45704579946446572f * y) * (1.0f - 5.0f * z2);
-    case 12: return (0.3731763325901154f * z) * (5.0f * z2 - 3.0f);
-    case 13: return (0.45704579946446572f * x) * (1.0f - 5.0f * z2);
-    case 14: return (1.4453057213202769f * z) * (x2 - y2);
-    default: return (0.59004358992664352f * x) * (-x2 + 3.0f * y2);
-  }
-}
 
 // one thread per (sample, float4 of hx); rows of hx are 64 floats.  (r06: was one thread per column -- a 64-bit division per element and a 16-way divergent
 // switch over the SH polynomials; 133 us in the traced step of config 4, on the chain field forward -> field backward -> tile pass.  Same expressions per element.)

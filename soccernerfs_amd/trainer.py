@@ -34,6 +34,10 @@ class KPlanesTrainConfig:
     proposal_feature_dim: int = 8
     sigma_net_hidden_dim: int = 128
     rgb_net_hidden_dim: int = 64
+    # KPlanesModelConfig.disable_viewing_dependent (NS/models/kplanes.py:145): True = the `k-planes` preset (colour net on the 15 geometry
+    # features); False = the reference class's default, colour net on [SH degree 4 of the direction (16) | geometry features (15)]
+    # (NS/fields/kplanes_field.py:206-216, :260-262, :314-323; csrc/color_vd.hip)
+    disable_viewing_dependent: bool = True
     num_proposal_samples_per_ray: Tuple[int, ...] = (256, 128)
     num_nerf_samples_per_ray: int = 64
     use_single_jitter: bool = False
@@ -228,7 +232,8 @@ class KPlanesTrainer:
 
         self.field_planes = PlaneSet(cfg.feature_dim, reso, concat=True, a=0.1, b=0.5, generator=gen)
         self.sigma_net = mlp(cfg.feature_dim * len(reso), 16, cfg.sigma_net_hidden_dim, 1, "None", cfg.sigma_operands)
-        self.color_net = mlp(15, 3, cfg.rgb_net_hidden_dim, 2, "Sigmoid", cfg.color_operands)
+        self.view_dependent = not cfg.disable_viewing_dependent
+        self.color_net = mlp(31 if self.view_dependent else 15, 3, cfg.rgb_net_hidden_dim, 2, "Sigmoid", cfg.color_operands)
         self.prop_planes = [PlaneSet(cfg.proposal_feature_dim, [list(r)], concat=False, a=0.1, b=0.15, generator=gen)
                             for r in cfg.proposal_resolutions]
         self.prop_nets = [mlp(cfg.proposal_feature_dim, 1, 64, 1, "None", cfg.proposal_operands) for _ in cfg.proposal_resolutions]
@@ -334,6 +339,12 @@ class KPlanesTrainer:
         self._desc_prop = [p.desc() for p in self.prop_planes]
         self.fused_field = bool(cfg.fused_field and self.lib.snerf_kplanes_field_fwd_supported(
             C.byref(self._desc_field), C.byref(self.sigma_net.desc), C.byref(self.color_net.desc)))
+        # view-dependent colour net: with 16-bit operands its backward forms [SH | h] on chip (snerf_kplanes_color_bwd_vd); the generic MLP kernels
+        # (exact fp32 operands, the unfused forward, deterministic mode) read it from cx [N, 32] (snerf_kplanes_color_input_fwd) and write gcx
+        self.color_bwd_vd = bool(self.view_dependent and not cfg.deterministic and self.lib.snerf_kplanes_color_bwd_vd_supported(C.byref(self.color_net.desc)))
+        if self.view_dependent and not (self.fused_field and self.color_bwd_vd):
+            self.buf["cx"] = f(R * S2, 32)
+            self.buf["gcx"] = f(R * S2, 32)
         if self.fused_field:  # the forward's operand-typed feature tile, kept for the unfused backward (snerf_mlp_bwd_x16)
             dt16 = torch.bfloat16 if self.sigma_net.desc.operands == 1 else torch.float16
             self.buf["feat16"] = torch.empty(R * self.S[2], self.field_planes.out_dim, dtype=dt16, device=self.dev)
@@ -475,6 +486,39 @@ class KPlanesTrainer:
                       self._p(gY) if gY is not None else None, ldgy, aux_col, self._p(gaux) if gaux is not None else None,
                       self._p(gX) if gX is not None else None, ldgx, self._p(gw), self._st), "mlp_bwd")
 
+    def _color_input(self, dirs, N, h, cx):
+        """cx[:N] = [SH4 of the ray directions | h[:, :15] | 0] (view-dependent colour net, generic MLP kernels)."""
+        with self._span("kplanes_color_input_fwd"):
+            _lib.check(self.lib.snerf_kplanes_color_input_fwd(self._p(dirs), self.S[2], self._p(h), C.c_int64(N), self._p(cx), self._st), "color_input_fwd")
+
+    def _color_backward(self, r0: int, r1: int):
+        """Colour-net backward for rays [r0, r1): d loss / d weights -> field.color, d loss / d h[:, :15] -> gh[:, :15] (gh[:, 15] stays 0: the density
+        enters the sigma_net backward through gaux)."""
+        b, S2 = self.buf, self.S[2]
+        n0, N = r0 * S2, (r1 - r0) * S2
+        sl = lambda t: t[n0:n0 + N]
+        if not self.view_dependent:
+            # X = h[:, :15] (stride 16); its gX lands in gh[:, :15]
+            self._mlp_bwd(self.color_net, "field.color", sl(b["h"]), 16, N, sl(b["grgb"]), 3, -1, None, sl(b["gh"]), 16)
+            return
+        dirs = self.rays["directions"][r0:r1]
+        if self.color_bwd_vd:  # X = [SH | h[:, :15]] formed on chip from the ray directions; gX straight into gh[:, :15]
+            net, ws = self.color_net, self._mlp_ws.get("field.color")
+            with self._span("color_bwd_vd"):
+                if ws is not None:
+                    self._ws_dirty.add("field.color")
+                    _lib.check(self.lib.snerf_kplanes_color_bwd_vd_ws(C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), C.c_int64(N),
+                                                                      self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(ws), self._st), "color_bwd_vd_ws")
+                else:
+                    _lib.check(self.lib.snerf_kplanes_color_bwd_vd(C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), C.c_int64(N),
+                                                                   self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(self.gviews["field.color"]), self._st),
+                               "color_bwd_vd")
+            return
+        self._color_input(dirs, N, sl(b["h"]), sl(b["cx"]))
+        self._mlp_bwd(self.color_net, "field.color", sl(b["cx"]), 32, N, sl(b["grgb"]), 3, -1, None, sl(b["gcx"]), 32)
+        with self._span("kplanes_color_input_bwd"):
+            _lib.check(self.lib.snerf_kplanes_color_input_bwd(self._p(sl(b["gcx"])), 32, C.c_int64(N), self._p(sl(b["gh"])), self._st), "color_input_bwd")
+
     def _reduce_mlp_grads(self, names):
         """Folds the weight-gradient workspaces of `names` into self.grads (current stream) and clears them; only those a backward kernel of this
         step has written."""
@@ -580,7 +624,11 @@ class KPlanesTrainer:
                     self._issue_sort(co)
                 if not self._fwd_fused:
                     self._mlp_fwd(self.sigma_net, b["feat"], self.field_planes.out_dim, N, b["h"], 16, 15, b["dens"][2])
-                    self._mlp_fwd(self.color_net, b["h"], 16, N, b["rgb"], 3)
+                    if self.view_dependent:
+                        self._color_input(d, N, b["h"], b["cx"])
+                        self._mlp_fwd(self.color_net, b["cx"], 32, N, b["rgb"], 3)
+                    else:
+                        self._mlp_fwd(self.color_net, b["h"], 16, N, b["rgb"], 3)
                 self._render_deferred = bool(training and defer_render)
                 if not self._render_deferred:
                     _lib.check(self.lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), R, self.S[2], self._p(b["w"][2]), self._st), "weights_fwd")
@@ -672,8 +720,7 @@ class KPlanesTrainer:
         b, S2, F = self.buf, self.S[2], self.field_planes.out_dim
         n0, N = r0 * S2, (r1 - r0) * S2
         sl = lambda t: t[n0:n0 + N]
-        # colour net: X = h[:, :15] (stride 16); its gX lands in gh[:, :15]; gh[:, 15] stays 0 (density enters through gaux)
-        self._mlp_bwd(self.color_net, "field.color", sl(b["h"]), 16, N, sl(b["grgb"]), 3, -1, None, sl(b["gh"]), 16)
+        self._color_backward(r0, r1)
         qg = bool(self._qg_step and self._sort_done is not None and r0 == 0 and r1 == self.R)
         if qg:
             ss = self._ss

@@ -65,6 +65,7 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
     torch.manual_seed(seed)
     random.seed(seed)
     cfg = KPlanesTrainConfig(max_steps=args.schedule_steps, mlp_operands=args.mlp_operands, seed=seed, deterministic=args.deterministic,
+                             disable_viewing_dependent=not args.view_dependent,
                              nonfinite_policy=args.nonfinite_policy, fused_field=not args.no_fused_field, quotient_scatter=not args.no_quotient_scatter, gvec_dtype=args.gvec_dtype,
                              emulate_transports=args.emulate_transports, quotient_epilogue=not args.no_quotient_epilogue, fused_proposal=not args.no_fused_proposal,
                              sigma_operands=args.sigma_operands, color_operands=args.color_operands, proposal_operands=args.proposal_operands)
@@ -162,6 +163,7 @@ def main():
     ap.add_argument("--color-operands", default=None)
     ap.add_argument("--proposal-operands", default=None)
     ap.add_argument("--deterministic", action="store_true", help="fixed-point gradient accumulation: bit-identical reruns")
+    ap.add_argument("--view-dependent", action="store_true", help="colour net on [SH4 of the direction | geometry features] (KPlanesModelConfig's class default)")
     ap.add_argument("--nonfinite-policy", default="skip_step", choices=["skip_step", "drop_elements"])
     ap.add_argument("--no-fused-field", action="store_true", help="unfused forward kernels")
     ap.add_argument("--no-quotient-epilogue", action="store_true", help="round 3's flow: G = gfeat .* feat from the separate pass over fp32 features (A-B)")
@@ -203,7 +205,7 @@ def main():
            if args.standin else "soccernerfs_amd KPlanesTrainer (HIP)",
            "oracle_init": bool(args.oracle_init or args.standin),
            "mlp_operands": args.mlp_operands, "gvec_dtype": args.gvec_dtype, "per_net_operands": [args.sigma_operands, args.color_operands, args.proposal_operands],
-           "deterministic": args.deterministic, "nonfinite_policy": args.nonfinite_policy,
+           "deterministic": args.deterministic, "view_dependent": args.view_dependent, "nonfinite_policy": args.nonfinite_policy,
            "emulate_transports": args.emulate_transports, "time_sorted_rays": args.time_sorted_rays, "fused_field": not args.no_fused_field, "quotient_scatter": not args.no_quotient_scatter,
            "quotient_epilogue": not args.no_quotient_epilogue, "fused_proposal": not args.no_fused_proposal,
            "eval_sets": {"camera_20": "20th arc camera (reference 'all' split eval camera; extrapolated view), %d frames" % len(sets["camera_20"][1]),

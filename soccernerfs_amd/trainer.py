@@ -10,13 +10,13 @@ one fused Adam sweep that also clears the gradients.  `soccernerfs_amd.kplanes.K
 nerfstudio-shaped (autograd) face of the same kernels; tests check the two against each other and the oracle.
 """
 import ctypes as C
-import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, ops
+from .fused_step import FusedStep, _On, _align4, anneal_value, cosine_lr_factor, update_schedule  # noqa: F401 (the schedules are imported from here)
 from .streams import side_stream
 from .plane_set import PlaneSet
 from .tcnn_compat import Network
@@ -149,30 +149,7 @@ class KPlanesTrainConfig:
     pipeline_sweep: str = ""
 
 
-def anneal_value(step: int, max_iters: int, slope: float) -> float:
-    """set_anneal callback (NS/models/kplanes.py:326-331)."""
-    frac = min(max(step / max_iters, 0.0), 1.0)
-    return (slope * frac) / ((slope - 1) * frac + 1)
-
-
-def update_schedule(step: int, warmup: int, every: int) -> float:
-    """NS/models/kplanes.py:254-259."""
-    return min(max(every * min(max(step / warmup, 0.0), 1.0), 1.0), float(every))
-
-
-def cosine_lr_factor(step: int, warm_up_end: int, max_steps: int, alpha: float) -> float:
-    """CosineDecayScheduler (NS/engine/schedulers.py:126-141)."""
-    if step < warm_up_end:
-        return step / warm_up_end
-    progress = (step - warm_up_end) / (max_steps - warm_up_end)
-    return (math.cos(math.pi * progress) + 1.0) * 0.5 * (1 - alpha) + alpha
-
-
-def _align4(n: int) -> int:
-    return (n + 3) // 4 * 4
-
-
-class KPlanesTrainer:
+class KPlanesTrainer(FusedStep):
     """Owns parameters (one flat fp32 buffer), Adam state and all work buffers for a fixed ray batch size R."""
 
     def __init__(self, cfg: KPlanesTrainConfig, num_rays: int, device="cuda:0", process_group=None):
@@ -238,26 +215,12 @@ class KPlanesTrainer:
                             for r in cfg.proposal_resolutions]
         self.prop_nets = [mlp(cfg.proposal_feature_dim, 1, 64, 1, "None", cfg.proposal_operands) for _ in cfg.proposal_resolutions]
         # ---- flatten: [proposal_networks | fields], each segment 16-B aligned ----
-        self.segments = []  # (name, module, attr, offset, numel)
-        off = 0
-        for i, (pp, pn) in enumerate(zip(self.prop_planes, self.prop_nets)):
-            for name, mod, attr in ((f"prop{i}.planes", pp, "planes"), (f"prop{i}.mlp", pn, "params")):
-                n = getattr(mod, attr).numel()
-                self.segments.append((name, mod, attr, off, n))
-                off += _align4(n)
-        self.n_proposal_params = off
-        for name, mod, attr in (("field.planes", self.field_planes, "planes"), ("field.sigma", self.sigma_net, "params"),
-                                ("field.color", self.color_net, "params")):
-            n = getattr(mod, attr).numel()
-            self.segments.append((name, mod, attr, off, n))
-            if name == "field.planes":
-                # padded so that the segment splits into `world` equal float4-aligned optimiser shards; the pad stays zero
-                q = 4 * self.world
-                self._field_seg = (off, n, (n + q - 1) // q * q)
-                off += self._field_seg[2]
-            else:
-                off += _align4(n)
-        self.n_params = off
+        order = [(f"prop{i}.{k}", mod, attr) for i, (pp, pn) in enumerate(zip(self.prop_planes, self.prop_nets)) for k, mod, attr in (("planes", pp, "planes"), ("mlp", pn, "params"))]
+        order += [("field.planes", self.field_planes, "planes"), ("field.sigma", self.sigma_net, "params"), ("field.color", self.color_net, "params")]
+        # field.planes is padded so that the segment splits into `world` equal float4-aligned optimiser shards; the pad stays zero
+        super().__init__(order, self.dev, deterministic=cfg.deterministic, shaped=False, pad_to={"field.planes": 4 * self.world})
+        o, n = self.off["field.planes"]
+        self.n_proposal_params, self._field_seg = o, (o, n, self.off["field.sigma"][0] - o)
         from .exchange_plan import kplanes_segment_sizes
 
         # the tensor-free restatement of this layout (what tests/test_exchange_plan_cpu.py checks at world 2 / 4 / 8) must describe THIS buffer
@@ -265,21 +228,10 @@ class KPlanesTrainer:
                                    {"prop": self.prop_nets[0].params.numel(), "sigma": self.sigma_net.params.numel(), "color": self.color_net.params.numel()}, self.world)
         assert (sz["n_params"], sz["n_proposal_params"], sz["field_offset"], sz["field_floats"], sz["field_padded"]) == \
             (self.n_params, self.n_proposal_params) + tuple(self._field_seg), (sz, self.n_params, self._field_seg)
-        self.params = torch.zeros(off, dtype=torch.float32, device=self.dev)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.views, self.gviews, self.mviews, self.vviews = {}, {}, {}, {}
-        for name, mod, attr, o, n in self.segments:
-            self.params[o:o + n].copy_(getattr(mod, attr).detach())
-            self.gviews[name], self.mviews[name], self.vviews[name] = self.grads[o:o + n], self.exp_avg[o:o + n], self.exp_avg_sq[o:o + n]
-        self._repoint(self.params)
         # device-resident optimiser state per parameter group (= per torch optimiser of the reference, kplanes.py:311-316): skip-step flag,
         # Adam step counter, counters of skipped steps / dropped elements (include/snerf.h: snerf_adam_dyn)
         self._dyn = {"fields": ops.new_adam_dyn(self.dev), "proposal_networks": ops.new_adam_dyn(self.dev)}
         self._prepared = set()
-        # deterministic mode: gradients accumulate as 64-bit fixed point (same layout as self.grads) and are converted once per step
-        self.grads_fx = torch.zeros(off, dtype=torch.int64, device=self.dev) if cfg.deterministic else None
         # the regulariser-fused optimiser sweep reads neighbours of the OLD parameters: parameters ping-pong between two buffers
         self.fuse_reg_into_adam = cfg.fuse_reg_into_adam
         self._params_alt = torch.zeros_like(self.params)
@@ -305,7 +257,6 @@ class KPlanesTrainer:
             "depth_rays": [f(R), f(R), f(R)],
             "reg": torch.zeros(3, ops.REG_SLOTS, 16, dtype=torch.float32, device=self.dev),  # [field|prop0|prop1][slot][16]
         }
-        self._timing, self._timing_all = None, False
         # sorted plane-gradient scatter for the main field (csrc/kplanes_sorted.hip): ~6x fewer atomic requests
         self.sorted_scatter = cfg.sorted_scatter
         self._gvec_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[cfg.gvec_dtype]
@@ -380,52 +331,6 @@ class KPlanesTrainer:
             self._exchange.append({"lo": ch["lo"], "hi": ch["hi"], "shard": shard, "g_shard": f(shard), "p_shard": f(shard), "rs": None, "ag": None,
                                    "g16": None, "g16_shard": None, "d16_full": None, "d16_shard": None})
 
-    def _repoint(self, flat: torch.Tensor):
-        """Make `flat` the live parameter buffer: module parameters and self.views alias its segments."""
-        self.params = flat
-        for name, mod, attr, o, n in self.segments:
-            getattr(mod, attr).data = flat[o:o + n]
-            self.views[name] = flat[o:o + n]
-
-    # -------------------------------------------------------------------------------------------
-    def enable_kernel_timing(self, names=None):
-        """Record HIP events (on the launch stream) around kernel groups; `names` = None times every group.
-        Read back with `kernel_times_ms()` (synchronises)."""
-        self._timing = {} if names is None else {n: [] for n in names}
-        self._timing_all = names is None
-
-    def disable_kernel_timing(self):
-        self._timing = None
-
-    def kernel_times_ms(self) -> Dict[str, Tuple[float, int]]:
-        """name -> (mean milliseconds per launch, launches)."""
-        torch.cuda.synchronize()
-        out = {}
-        for k, evs in (self._timing or {}).items():
-            if evs:
-                out[k] = (sum(a.elapsed_time(b) for a, b in evs) / len(evs), len(evs))
-        return out
-
-    class _Span:
-        def __init__(self, tr, name):
-            self.tr, self.name = tr, name
-
-        def __enter__(self):
-            t = self.tr._timing
-            self.on = t is not None and (self.tr._timing_all or self.name in t)
-            if self.on:
-                self.a = torch.cuda.Event(enable_timing=True)
-                self.a.record()
-
-        def __exit__(self, *exc):
-            if self.on:
-                b = torch.cuda.Event(enable_timing=True)
-                b.record()
-                self.tr._timing.setdefault(self.name, []).append((self.a, b))
-
-    def _span(self, name):
-        return KPlanesTrainer._Span(self, name)
-
     COMM_WAIT_SPANS = ("comm_wait.reduce_scatter", "comm_wait.all_gather", "comm_wait.all_reduce", "comm_wait.flags", "allreduce_grads")
 
     def _comm_wait(self, work, name: str):
@@ -443,48 +348,33 @@ class KPlanesTrainer:
 
         return link_bytes(self.world, self.n_params, self._field_seg[2], self.buf["reg"][0].numel(), self._sharded(), self.grad_transport, self.param_transport)
 
-    def _p(self, t):
-        return C.c_void_p(t.data_ptr())
-
     def _gather(self, desc, planes, coords, N, out):
       with self._span("kplanes_gather_fwd.field" if desc is self._desc_field else "kplanes_gather_fwd.prop"):
         _lib.check(self.lib.snerf_kplanes_gather_fwd(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(out), self._st), "gather_fwd")
-
-    def _fx(self, gview: torch.Tensor) -> torch.Tensor:
-        """The fixed-point cells behind a view of self.grads (deterministic mode)."""
-        o = gview.storage_offset() - self.grads.storage_offset()
-        return self.grads_fx[o:o + gview.numel()]
 
     def _scatter(self, desc, planes, coords, N, gout, gplanes):
       with self._span("kplanes_gather_bwd.field" if desc is self._desc_field else "kplanes_gather_bwd.prop"):
         if self.grads_fx is not None:
             _lib.check(self.lib.snerf_kplanes_gather_bwd_fx(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gout),
-                                                            self._p(self._fx(gplanes)), self._st), "gather_bwd_fx")
+                                                            self._p(self.fx(gplanes)), self._st), "gather_bwd_fx")
         else:
             _lib.check(self.lib.snerf_kplanes_gather_bwd(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gout), self._p(gplanes),
                                                          self._st), "gather_bwd")
 
-    def _mlp_fwd(self, net, X, ldx, N, Y, ldy, aux_col=-1, aux=None):
-      with self._span(f"mlp_fwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
-        _lib.check(self.lib.snerf_mlp_fwd(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N), self._p(Y), ldy, aux_col,
-                                          self._p(aux) if aux is not None else None, self._st), "mlp_fwd")
-
     def _mlp_bwd(self, net, gname, X, ldx, N, gY, ldgy, aux_col, gaux, gX, ldgx, x16=False):
-      with self._span(f"mlp_bwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
+        """FusedStep._mlp_bwd for the net whose gradient segment is `gname`, through its weight-gradient workspace where it has one;
+        x16: X is the forward's operand-typed feature tile (snerf_mlp_bwd_x16)."""
         ws = self._mlp_ws.get(gname) if not x16 else None
-        if ws is not None:
-            self._ws_dirty.add(gname)
-            _lib.check(self.lib.snerf_mlp_bwd_ws(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N),
-                                                 self._p(gY) if gY is not None else None, ldgy, aux_col, self._p(gaux) if gaux is not None else None,
-                                                 self._p(gX) if gX is not None else None, ldgx, self._p(ws), self._st), "mlp_bwd_ws")
-            return
-        fn = self.lib.snerf_mlp_bwd_fx if self.grads_fx is not None else (self.lib.snerf_mlp_bwd_x16 if x16 else self.lib.snerf_mlp_bwd)
-        if x16 and self.grads_fx is not None:  # deterministic mode: the fixed-point kernel takes fp32 inputs (exact image of the 16-bit tile)
-            X = X.float()
-        gw = self._fx(self.gviews[gname]) if self.grads_fx is not None else self.gviews[gname]
-        _lib.check(fn(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N),
-                      self._p(gY) if gY is not None else None, ldgy, aux_col, self._p(gaux) if gaux is not None else None,
-                      self._p(gX) if gX is not None else None, ldgx, self._p(gw), self._st), "mlp_bwd")
+        if ws is None and not (x16 and self.grads_fx is None):
+            # deterministic mode: the fixed-point kernel takes fp32 inputs (exact image of the 16-bit tile)
+            return FusedStep._mlp_bwd(self, net, self.gviews[gname], X.float() if x16 else X, ldx, N, gY, ldgy, aux_col, gaux, gX, ldgx)
+        with self._span(f"mlp_bwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
+            if ws is not None:
+                self._ws_dirty.add(gname)
+            fn, what = (self.lib.snerf_mlp_bwd_ws, "mlp_bwd_ws") if ws is not None else (self.lib.snerf_mlp_bwd_x16, "mlp_bwd")
+            _lib.check(fn(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N), self._p(gY) if gY is not None else None, ldgy, aux_col,
+                          self._p(gaux) if gaux is not None else None, self._p(gX) if gX is not None else None, ldgx,
+                          self._p(ws if ws is not None else self.gviews[gname]), self._st), what)
 
     def _color_input(self, dirs, N, h, cx):
         """cx[:N] = [SH4 of the ray directions | h[:, :15] | 0] (view-dependent colour net, generic MLP kernels)."""
@@ -529,21 +419,6 @@ class KPlanesTrainer:
                     _lib.check(self.lib.snerf_mlp_gw_reduce(C.byref(net.desc), self._p(self._mlp_ws[gname]), self._p(self.gviews[gname]), self._st), "mlp_gw_reduce")
                 self._ws_dirty.discard(gname)
 
-    def _resample(self, lvl, rand, anneal):
-        """density[lvl] -> weights[lvl] (stored) -> PDF sample level lvl+1 bins."""
-        b, a = self.buf, _lib.ResampleArgs()
-        a.density, a.ebins_prev, a.weights_out = b["dens"][lvl].data_ptr(), b["eb"][lvl].data_ptr(), b["w"][lvl].data_ptr()
-        a.sbins_prev, a.nears, a.fars = b["sb"][lvl].data_ptr(), self.rays["nears"].data_ptr(), self.rays["fars"].data_ptr()
-        if rand is None:
-            a.u_mode = 2
-        else:
-            a.u_mode, a.u_or_rand, a.rand_cols = 1, rand.data_ptr(), rand.shape[-1]
-        a.sbins_out, a.ebins_out = b["sb"][lvl + 1].data_ptr(), b["eb"][lvl + 1].data_ptr()
-        a.R, a.S_prev, a.S, a.kind = self._fwd_rays, self.S[lvl], self.S[lvl + 1], 0
-        a.anneal, a.histogram_padding, a.eps = anneal, 0.01, 1e-5
-        with self._span("pdf_resample"):
-            _lib.check(self.lib.snerf_pdf_resample(C.byref(a), self._st), "pdf_resample")
-
     # -------------------------------------------------------------------------------------------
     def forward(self, rays: Dict[str, torch.Tensor], rng: Optional[Dict[str, torch.Tensor]], anneal: float, training: bool = True,
                 defer_render: bool = False):
@@ -574,10 +449,7 @@ class KPlanesTrainer:
         else:
             rays["nears"], rays["fars"] = ops._f32c(rays["nears"], "rays['nears']"), ops._f32c(rays["fars"], "rays['fars']")
         self.rays = rays
-        t_rand = rng["t_rand"] if training else None
-        _lib.check(self.lib.snerf_spaced_bins(self._p(rays["nears"]), self._p(rays["fars"]), self._p(t_rand) if t_rand is not None else None,
-                                              t_rand.shape[-1] if t_rand is not None else 0, R, self.S[0], 0, self._p(b["sb"][0]), self._p(b["eb"][0]),
-                                              self._st), "spaced_bins")
+        self._spaced_bins(rng["t_rand"] if training else None)
         self._coords = []
         for lvl in range(3):
             rescale = lvl == 2  # proposal fields keep [0,1] coordinates (kplanes_field.py:440), the main field maps to [-1,1] (:283-284)
@@ -634,15 +506,10 @@ class KPlanesTrainer:
                     _lib.check(self.lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), R, self.S[2], self._p(b["w"][2]), self._st), "weights_fwd")
         if self._render_deferred:
             return b["rgb_out"][:R]
-        a = _lib.RenderArgs()
-        a.weights, a.rgb, a.ebins = b["w"][2].data_ptr(), b["rgb"].data_ptr(), b["eb"][2].data_ptr()
         if training:
-            a.bg_mode, a.bg = 0, rng["bg"].data_ptr()
+            self._render_fwd(True, 0, rng["bg"], "depth_median")
         else:
-            a.bg_mode = 1
-        a.R, a.S, a.training = R, self.S[2], int(training)
-        a.rgb_out, a.acc_out, a.depth_median = b["rgb_out"].data_ptr(), b["acc"].data_ptr(), b["depth"].data_ptr()
-        _lib.check(self.lib.snerf_render_fwd(C.byref(a), self._st), "render_fwd")
+            self._render_fwd(False, 1, None, "depth_median")
         return b["rgb_out"][:R]
 
     def _issue_sort(self, co):
@@ -654,27 +521,11 @@ class KPlanesTrainer:
         if self._passb_done is not None:
             st.wait_event(self._passb_done)
             self._passb_done = None
-        with KPlanesTrainer._On(self, st), self._span("kplanes_sort"):
+        with _On(self, st), self._span("kplanes_sort"):
             self._ss.sort(co, self._st)
         self._sort_done = st.record_event()
 
-    # ---- stream helpers: kernels bound by different units overlap on separate HIP streams ----
-    class _On:
-        """Run the enclosed launches on `stream` (torch's current stream AND the stream handed to libsnerf)."""
-
-        def __init__(self, tr, stream):
-            self.tr, self.stream = tr, stream
-
-        def __enter__(self):
-            self.prev = self.tr._st
-            self.ctx = torch.cuda.stream(self.stream)
-            self.ctx.__enter__()
-            self.tr._st = C.c_void_p(self.stream.cuda_stream)
-
-        def __exit__(self, *exc):
-            self.tr._st = self.prev
-            self.ctx.__exit__(*exc)
-
+    # ---- stream helpers: kernels bound by different units overlap on separate HIP streams (fused_step._On) ----
     def _stream(self, role: str):
         """Side stream by role, created on first use (so the common path holds main + "sort" + "prop" + "adam" only: HIP multiplexes the
         normal-priority streams onto 3 hardware queues beside the null stream's -- tools/debug_queues.py -- and chains sharing a queue do
@@ -759,7 +610,7 @@ class KPlanesTrainer:
                     st = self._stream("adam")
                     st.wait_event(main.record_event())
                     st.wait_event(self._sort_done)
-                    with KPlanesTrainer._On(self, st):
+                    with _On(self, st):
                         if self.cfg.pipeline_sweep and ns > 1 and not self.cfg.emulate_transports:
                             fine_first = self.cfg.pipeline_sweep == "fine_first"
                             first, second = ((ns - 1, ns), (0, ns - 1)) if fine_first else ((0, ns - 1), (ns - 1, ns))
@@ -801,7 +652,7 @@ class KPlanesTrainer:
                     main = torch.cuda.current_stream()
                     st = self._stream("adam")
                     st.wait_stream(main)
-                    with KPlanesTrainer._On(self, st):
+                    with _On(self, st):
                         self._scatter_field_scales(co, 0, ns, fixup=False)
                     self._passb_done = st.record_event()
             else:
@@ -827,17 +678,12 @@ class KPlanesTrainer:
         sweep, whose small workgroups leave it no room (0.65 ms for a 0.03-ms kernel), and the chain ends after the sweep; the untraced step did
         not get faster with the interleaved order (see the config field), so the order stays as it was."""
         cfg, b, R, co = self.cfg, self.buf, self.R, self.cfg.loss_coefficients
-        S2 = self.S[2]
         for lvl in (0, 1):
-            Sp = self.S[lvl]
-            _lib.check(self.lib.snerf_interlevel(self._p(b["sb"][2]), self._p(b["w"][2]), S2, self._p(b["sb"][lvl]), self._p(b["w"][lvl]), Sp, R,
-                                                 co["interlevel_loss"] / (R * S2), self._p(b["inter_rays"][lvl]),
-                                                 self._p(b["gw"][lvl]) if proposal_grads else None, self._st), "interlevel")
+            self._interlevel(lvl, co["interlevel_loss"], proposal_grads)
             self._depth_loss(lvl, with_grad=proposal_grads)  # adds to the interlevel gradient just written
         if not proposal_grads:
             return
-        wb = lambda lvl: _lib.check(self.lib.snerf_weights_bwd(self._p(b["dens"][lvl]), self._p(b["eb"][lvl]), self._p(b["gw"][lvl]), R, self.S[lvl],
-                                                               self._p(b["gdens"][lvl]), 0, self._p(self._dyn["proposal_networks"]), self._st), "weights_bwd")
+        wb = lambda lvl: self._weights_bwd(lvl, self._dyn["proposal_networks"])
         nb = lambda lvl: self._mlp_bwd(self.prop_nets[lvl], f"prop{lvl}.mlp", b["pfeat"][lvl], cfg.proposal_feature_dim, R * self.S[lvl], None, 1, 0,
                                        b["gdens"][lvl], b["gpfeat"][lvl], cfg.proposal_feature_dim)
         sc = lambda lvl: self._scatter(self._desc_prop[lvl], self.prop_planes[lvl].planes, self._coords[lvl], R * self.S[lvl], b["gpfeat"][lvl],
@@ -873,7 +719,6 @@ class KPlanesTrainer:
         overlap: the regulariser sweep (HBM stream), the proposal-level backward (MFMA + atomics) and the field backward split
         into ray chunks whose MLP backward (MFMA) runs under the previous chunk's plane scatter (memory-side atomics)."""
         cfg, b, R, co = self.cfg, self.buf, self.R, self.cfg.loss_coefficients
-        S2 = self.S[2]
         main = torch.cuda.current_stream()
         self._reg_in_adam = not include_reg  # train_step: the regularisers' values and gradients come out of the optimiser sweep
         # depth supervision: termination depths [R] (batch["depth_image"]); None or a zero coefficient switches the term off
@@ -887,7 +732,7 @@ class KPlanesTrainer:
             if overlap:
                 st = self._stream("reg")
                 st.wait_stream(main)
-                with KPlanesTrainer._On(self, st):
+                with _On(self, st):
                     self._reg_sweep()
                 reg_done = st.record_event()  # every scatter adds on top of the STORED regulariser gradient
                 joins.append(st)
@@ -901,7 +746,7 @@ class KPlanesTrainer:
                 st.wait_event(reg_done)
             # (the two levels' chains are independent, but side by side on two streams they were no faster: 2.78 vs 2.72 ms; on a
             # high-priority stream -- a fifth hardware queue -- the whole step fell to 3.69 ms: profiles/r02_kernels.md section 8)
-            with KPlanesTrainer._On(self, st):
+            with _On(self, st):
                 self._proposal_backward(proposal_grads)
             joins.append(st)
 
@@ -915,29 +760,16 @@ class KPlanesTrainer:
             # The proposal chain reads the nerf level's weights, so it starts behind this kernel.
             assert self._depth is None, "depth supervision takes the separate kernels"
             self._render_deferred = False
-            ra = _lib.RayTrainArgs()
-            ra.density, ra.ebins, ra.sbins, ra.rgb = b["dens"][2].data_ptr(), b["eb"][2].data_ptr(), b["sb"][2].data_ptr(), b["rgb"].data_ptr()
-            ra.bg, ra.target, ra.R, ra.S, ra.bg_mode = rng["bg"].data_ptr(), target.data_ptr(), R, S2, 0
-            ra.go_scale, ra.dist_scale = 2.0 * co["rgb_loss"] / (3 * R), co["distortion_loss"] / R
-            ra.weights, ra.rgb_out, ra.acc_out, ra.depth_median = b["w"][2].data_ptr(), b["rgb_out"].data_ptr(), b["acc"].data_ptr(), b["depth"].data_ptr()
-            ra.sqerr_rays, ra.dist_rays, ra.g_rgb, ra.g_density = b["sqerr"].data_ptr(), b["dist_rays"].data_ptr(), b["grgb"].data_ptr(), b["gdens"][2].data_ptr()
-            ra.g_weights, ra.nonfinite_flag = None, self._dyn["fields"].data_ptr()
-            with self._span("ray_train_fwd_bwd"):
-                _lib.check(self.lib.snerf_ray_train_fwd_bwd(C.byref(ra), self._st), "ray_train_fwd_bwd")
+            self._ray_train(target, rng["bg"], 2.0 * co["rgb_loss"] / (3 * R), co["distortion_loss"] / R, True, self._dyn["fields"])
             if overlap and not sharded:
                 proposal_chain()
         else:
             if overlap and not sharded:
                 proposal_chain()
-            # MSELoss (kplanes.py:418) folded into the render backward: g_rgb_out = 2 c / (3R) * (rgb_out - target); value lazily from sqerr
-            _lib.check(self.lib.snerf_render_mse_bwd(self._p(b["w"][2]), self._p(b["rgb"]), self._p(rng["bg"]), 0, self._p(b["rgb_out"]), self._p(target),
-                                                     2.0 * co["rgb_loss"] / (3 * R), R, S2, self._p(b["gw"][2]), self._p(b["grgb"]), self._p(b["sqerr"]),
-                                                     self._st), "render_mse_bwd")
-            _lib.check(self.lib.snerf_distortion(self._p(b["w"][2]), self._p(b["sb"][2]), R, S2, co["distortion_loss"] / R, self._p(b["dist_rays"]),
-                                                 self._p(b["gw"][2]), 1, self._st), "distortion")
+            # MSELoss (kplanes.py:418): g_rgb_out = 2 c / (3R) * (rgb_out - target)
+            self._mse_distortion_bwd(target, rng["bg"], 2.0 * co["rgb_loss"] / (3 * R), co["distortion_loss"] / R)
             self._depth_loss(2, with_grad=True)
-            _lib.check(self.lib.snerf_weights_bwd(self._p(b["dens"][2]), self._p(b["eb"][2]), self._p(b["gw"][2]), R, S2, self._p(b["gdens"][2]), 0,
-                                                  self._p(self._dyn["fields"]), self._st), "weights_bwd")
+            self._weights_bwd(2, self._dyn["fields"])
         if reg_done is not None:
             main.wait_event(reg_done)
         # the field chain stays on the caller's stream: every extra stream is one more HIP stream competing for the (four) hardware queues, and
@@ -1023,7 +855,7 @@ class KPlanesTrainer:
         self._join_prop()
         self._wait_params()
         torch.cuda.synchronize(self.dev)
-        if check_overflow and getattr(self, "_fix_peak_host", None) is not None:
+        if check_overflow and self._fix_peak_host is not None:
             self._ss.check_fix_overflow()
 
     @torch.no_grad()
@@ -1039,7 +871,7 @@ class KPlanesTrainer:
             d.zero_()
         self.step = self._dyn_step = 0
         self._steps_since_update = 0
-        if getattr(self, "_fix_peak_host", None) is not None:  # a new run: the sticky overflow record of the old one is void
+        if self._fix_peak_host is not None:  # a new run: the sticky overflow record of the old one is void
             self._ss.clear_fix_overflow()
             self._fix_peak_host.zero_()
         torch.cuda.synchronize(self.dev)
@@ -1121,7 +953,7 @@ class KPlanesTrainer:
         cfg, co = self.cfg, self.cfg.loss_coefficients
         lr = cfg.lr * cosine_lr_factor(self.step, cfg.warm_up_end, cfg.max_steps, cfg.lr_alpha)
         gs = 1.0 / self.world
-        off = {name: (o, n) for name, _, _, o, n in self.segments}
+        off = self.off
         o, n, npad = self._field_seg
         new = self._params_alt
         self._convert_fx(0, o)
@@ -1189,7 +1021,7 @@ class KPlanesTrainer:
             o1, n1 = off["field.color"]
             dyn_f, dyn_p = self._dyn["fields"], self._dyn["proposal_networks"]
             for (o, n), dyn in ((off["prop0.mlp"], dyn_p), (off["prop1.mlp"], dyn_p), ((o0, o1 + n1 - o0), dyn_f)):
-                n4 = (n + 3) // 4 * 4
+                n4 = _align4(n)
                 ops.adam_step(self.params[o:o + n4], self.grads[o:o + n4], self.exp_avg[o:o + n4], self.exp_avg_sq[o:o + n4], self.step + 1, lr,
                               eps=self.cfg.adam_eps, grad_scale=gs, zero_grad=True, p_out=new[o:o + n4], dyn=dyn)
 
@@ -1205,7 +1037,7 @@ class KPlanesTrainer:
         lr = cfg.lr * cosine_lr_factor(self.step, cfg.warm_up_end, cfg.max_steps, cfg.lr_alpha)
         n4 = _align4(self.field_planes.numel)
         rng_ = (lo, n4 if hi is None else hi)
-        o, n = next((o, n) for name, _, _, o, n in self.segments if name == "field.planes")
+        o, n = self.off["field.planes"]
         args = (self.field_planes, self.params[o:o + n], self._params_alt[o:o + n], self.gviews["field.planes"], self.mviews["field.planes"],
                 self.vviews["field.planes"], tuple(co[k] for k in ("space_tv_loss", "time_smoothness_loss", "sparse_transients_loss")),
                 self.buf["reg"][0], self.step + 1, lr)
@@ -1220,7 +1052,7 @@ class KPlanesTrainer:
         st.wait_stream(cur)
         if after is not None:
             st.wait_event(after)
-        with KPlanesTrainer._On(self, st), self._span(span):
+        with _On(self, st), self._span(span):
             ops.adam_planes_step(*args, **kw)
 
     def allreduce_grads(self):
@@ -1258,7 +1090,7 @@ class KPlanesTrainer:
         # regularisers fused into the sweep: plane sets go through snerf_adam_planes_step (values land in buf["reg"]), the MLP
         # segments through the plain kernel; everything writes the OTHER parameter buffer, which then becomes live
         new = self._params_alt
-        off = {name: (o, n) for name, _, _, o, n in self.segments}
+        off = self.off
         sl = lambda t, name: t[off[name][0]:off[name][0] + off[name][1]]
         async_field = self.async_field_adam and self.overlap
         if not self._reg_zeroed:
@@ -1287,8 +1119,8 @@ class KPlanesTrainer:
             self._adam_field_range(0, None, side=async_field)
             self.field_sweep_launches = 1
         if emu in ("param", "both"):  # new = old + bf16(new - old) on the field planes, on the stream that ran the sweep
-            o_, n_ = next((o, n) for name, _, _, o, n in self.segments if name == "field.planes")
-            with KPlanesTrainer._On(self, self._stream("adam") if async_field else torch.cuda.current_stream()):
+            o_, n_ = self.off["field.planes"]
+            with _On(self, self._stream("adam") if async_field else torch.cuda.current_stream()):
                 old_, new_ = self.params[o_:o_ + n_], self._params_alt[o_:o_ + n_]
                 new_.copy_(old_ + (new_ - old_).to(torch.bfloat16).float())
         if async_field:

@@ -31,9 +31,13 @@ typedef void* snerf_stream_t; /* hipStream_t */
 
 #define SNERF_MAX_SCALES 8
 #define SNERF_ABI_VERSION 16
+/* Additions that leave every ABI-16 entry point and struct as it was count a REVISION instead of a new version, so that callers pinned to
+ * version 16 keep loading.  Revision 1: snerf_raygen_frame, snerf_kplanes_field_render(_supported), snerf_abi_revision itself. */
+#define SNERF_ABI_REVISION 1
 
 /* Library identity / diagnostics. */
 int snerf_abi_version(void);
+int snerf_abi_revision(void);
 const char* snerf_last_error(void);
 /* Name of the gfx target the kernels were compiled for ("gfx950"). */
 const char* snerf_target_arch(void);
@@ -260,6 +264,27 @@ int snerf_kplanes_field_fwd_supported(const snerf_kplanes_desc* desc, const sner
 int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
                             const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
                             float* density, float* rgb, void* feat16, float* h, float* feat32, snerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 16 revision 1: the render tail of the K-Planes model in eval mode as ONE kernel, for whole frames (ns-render / ns-eval: scripts/render.py:60-131,
+ * Model.get_outputs_for_camera_ray_bundle NS/models/base_model.py:159-186 -> KPlanesModel.get_outputs NS/models/kplanes.py:349-392):
+ * KPlanesField.forward (NS/fields/kplanes_field.py:275-358) -> RaySamples.get_weights (NS/cameras/rays.py:127-149) -> RGBRenderer with
+ * background "last_sample", AccumulationRenderer, DepthRenderer median / expected, with the eval-mode nan_to_num and clamp
+ * (NS/model_components/renderers.py:58-140, :197-223, :226-287).  = snerf_kplanes_field_fwd -> snerf_weights_fwd -> snerf_render_fwd(training = 0,
+ * bg_mode = 1), bit for bit when transmittance_cutoff = 0; per-sample density and colour stay on chip (a workgroup owns a whole ray).
+ *   coords: mode 1 (per-ray origins / dirs / times + euclidean bin edges [R, S+1]); S a multiple of 32, <= 320; the net shapes and operand types
+ *   of snerf_kplanes_field_fwd (1-6 scales, plain and view-dependent colour net).  snerf_kplanes_field_render_supported tells.
+ *   transmittance_cutoff > 0: early ray termination (not in the reference).  Once exp(-sum sigma delta) over a ray's evaluated 32-sample tiles drops
+ *   below the cutoff its remaining tiles are skipped: their samples count as zero density and the background is the last evaluated sample's colour;
+ *   |rgb error| and |accumulation error| <= cutoff.  0 = never, the exact path.
+ *   outputs: rgb_out [R,3], acc_out [R]; optional (NULL = not written) depth_median [R], depth_expected [R] (unclipped, as snerf_render_fwd),
+ *   median_index [R], samples_done [R] = the number of samples of the ray that were evaluated (S when the ray was not terminated).
+ * ------------------------------------------------------------------------------------------------ */
+int snerf_kplanes_field_render_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* sigma, const snerf_mlp_desc* color, int32_t S);
+int snerf_kplanes_field_render(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int32_t R,
+                               const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
+                               float transmittance_cutoff, float* rgb_out, float* acc_out, float* depth_median, float* depth_expected,
+                               int64_t* median_index, int32_t* samples_done, snerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ABI 16: view-dependent colour net of the K-Planes field (KPlanesField with disable_viewing_dependent = False, the reference class's default:
@@ -516,6 +541,31 @@ typedef struct {
   float* fars;             /* [R] */
 } snerf_raygen_args;
 int snerf_raygen(const snerf_raygen_args* args, snerf_stream_t stream);
+
+/* ABI 16 revision 1: the rays of pixels [p0, p1) of ONE camera in row-major order, with no index table: Cameras.generate_rays(camera_indices = k)
+ * (NS/cameras/cameras.py:300-418: get_image_coords meshgrid :420-446, then _generate_rays_from_coords :505-741) + AABBBoxCollider in eval mode
+ * (NS/model_components/scene_colliders.py:59-95), as Model.get_outputs_for_camera_ray_bundle chunks a frame (NS/models/base_model.py:159-186).
+ * Ray r is pixel p0 + r = (row (p0 + r) / W, column (p0 + r) % W).  The arithmetic and its order are snerf_raygen's with collide = 1,
+ * training = 0: every output equals snerf_raygen on the meshgrid index table bit for bit.  times may be NULL. */
+typedef struct {
+  float fx, fy, cx, cy;
+  float c2w[12];           /* [3,4] row-major */
+  float time;
+  int32_t W, H;
+  int32_t _pad;
+  int64_t p0, p1;
+  float near_plane;        /* kept for symmetry with snerf_raygen_args: the collider ignores it outside training */
+  float aabb_min[3];
+  float aabb_max[3];
+  float* origins;          /* [p1 - p0, 3] */
+  float* dirs;             /* [p1 - p0, 3] */
+  float* pixel_area;       /* [p1 - p0] */
+  float* dir_norm;         /* [p1 - p0] */
+  float* times;            /* [p1 - p0] or NULL */
+  float* nears;            /* [p1 - p0] */
+  float* fars;             /* [p1 - p0] */
+} snerf_raygen_frame_args;
+int snerf_raygen_frame(const snerf_raygen_frame_args* args, snerf_stream_t stream);
 
 /* PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77): indices[R,3] = floor(u[R,3] * (M,H,W)) as int64 (image, row, col), fused
  * with collate_image_dataset_batch's gather (:111-123): target[R,3] = images[c,y,x,:] / 255 for a resident uint8 image cache

@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_PKG, "libsnerf.so")
 
 MAX_SCALES = 8
 ABI_VERSION = 16
+ABI_REVISION = 1  # additions on top of ABI 16 (include/snerf.h: SNERF_ABI_REVISION)
 
 
 class KPlanesDesc(C.Structure):
@@ -86,6 +87,15 @@ class RaygenArgs(C.Structure):
                 ("c2w", C.c_void_p), ("cam_times", C.c_void_p),
                 ("R", C.c_int32), ("collide", C.c_int32), ("training", C.c_int32), ("near_plane", C.c_float),
                 ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("origins", C.c_void_p), ("dirs", C.c_void_p), ("pixel_area", C.c_void_p), ("dir_norm", C.c_void_p),
+                ("times", C.c_void_p), ("nears", C.c_void_p), ("fars", C.c_void_p)]
+
+
+class RaygenFrameArgs(C.Structure):
+    """snerf_raygen_frame_args (ABI 16 revision 1, csrc/render_eval.hip): the rays of pixels [p0, p1) of one camera."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("c2w", C.c_float * 12), ("time", C.c_float),
+                ("W", C.c_int32), ("H", C.c_int32), ("_pad", C.c_int32), ("p0", C.c_int64), ("p1", C.c_int64),
+                ("near_plane", C.c_float), ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
                 ("origins", C.c_void_p), ("dirs", C.c_void_p), ("pixel_area", C.c_void_p), ("dir_norm", C.c_void_p),
                 ("times", C.c_void_p), ("nears", C.c_void_p), ("fars", C.c_void_p)]
 
@@ -172,8 +182,12 @@ def lib():
     l.snerf_adam_step_tv.argtypes = [P, P, P, P, L, I, I, I, P, F, F, F, F, I, F, I, P, P]
     l.snerf_isg_maps.argtypes = [P, I, I, I, I, I, P, P, P, I, F, P, P, P]
     l.snerf_ist_maps.argtypes = [P, I, I, I, I, P, P, F, P, P]
+    l.snerf_kplanes_field_render.argtypes = [P, P, P, I, P, P, P, P, F, P, P, P, P, P, P, P]
     if l.snerf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
+    revision = l.snerf_abi_revision() if hasattr(l, "snerf_abi_revision") else 0  # a library from before revisions were counted
+    if revision != ABI_REVISION:
+        raise RuntimeError(f"libsnerf ABI {ABI_VERSION} revision {revision} != binding revision {ABI_REVISION}: rebuild the library")
     _lib = l
     return l
 
@@ -187,6 +201,7 @@ def check(rc: int, what: str = ""):
 # every symbol include/snerf.h declares; tests/test_abi.py checks the list against the header
 EXPORTS = [
     "snerf_abi_version",
+    "snerf_abi_revision",
     "snerf_last_error",
     "snerf_target_arch",
     "snerf_kplanes_gather_fwd",
@@ -225,6 +240,7 @@ EXPORTS = [
     "snerf_sort_rays_by_key",
     "snerf_kplanes_scatter_sorted_scales",
     "snerf_raygen",
+    "snerf_raygen_frame",
     "snerf_aabb_collide",
     "snerf_tgrid_encode_fwd",
     "snerf_hashgrid_layout",
@@ -266,6 +282,8 @@ EXPORTS = [
     "snerf_urf_depth_loss",
     "snerf_kplanes_field_fwd",
     "snerf_kplanes_field_fwd_supported",
+    "snerf_kplanes_field_render",
+    "snerf_kplanes_field_render_supported",
     "snerf_kplanes_color_input_fwd",
     "snerf_kplanes_color_input_bwd",
     "snerf_kplanes_color_bwd_vd",

@@ -57,5 +57,6 @@ extern "C" int snerf_fx_to_float(int64_t* fx, float* out, int64_t n, int32_t acc
 }
 
 extern "C" int snerf_abi_version(void) { return SNERF_ABI_VERSION; }
+extern "C" int snerf_abi_revision(void) { return SNERF_ABI_REVISION; }
 extern "C" const char* snerf_last_error(void) { return snerf::g_err; }
 extern "C" const char* snerf_target_arch(void) { return "gfx950"; }

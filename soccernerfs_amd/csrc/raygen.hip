@@ -5,7 +5,7 @@
 // :704-741 -- ~40 small ATen kernels incl. boolean-mask scatters) and AABBBoxCollider._intersect_with_aabb
 // (NS/model_components/scene_colliders.py:59-95).  One lane per ray; the per-camera table (fx,fy,cx,cy,c2w,time)
 // is a few KB and stays in L1/L2.
-#include "common.hpp"
+#include "raygen_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -24,50 +24,17 @@ struct RaygenArgs {
   float* nears; float* fars;  // [R]
 };
 
-__device__ __forceinline__ void cam_to_world(const float* rot /*3x4 row-major*/, float x, float y, float z, float out[3], float& norm) {
-  float v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) v[i] = (x * rot[i * 4 + 0] + y * rot[i * 4 + 1]) + z * rot[i * 4 + 2];  // sum over the last axis (cameras.py:712-714)
-  norm = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-  // normalize_with_norm (NS/cameras/camera_utils.py:240-252): norm = max(|v|, 4*eps_f64); returns x / norm and norm
-  norm = fmaxf(norm, 8.8817841970012523e-16f);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) out[i] = v[i] / norm;
-}
-
 __global__ void raygen_kernel(RaygenArgs a) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.R) return;
   const int64_t c = a.indices[(int64_t)r * 3], yi = a.indices[(int64_t)r * 3 + 1], xi = a.indices[(int64_t)r * 3 + 2];
-  const float y = (float)yi + 0.5f, x = (float)xi + 0.5f;  // image_coords = pixel index + 0.5 (cameras.py:318-319)
-  const float fx = a.fx[c], fy = a.fy[c], cx = a.cx[c], cy = a.cy[c];
-  const float* m = a.c2w + c * 12;
-  float d0[3], dx[3], dy[3], n0, nx, ny;
-  cam_to_world(m, (x - cx) / fx, -(y - cy) / fy, -1.f, d0, n0);
-  cam_to_world(m, ((x + 1.f) - cx) / fx, -(y - cy) / fy, -1.f, dx, nx);
-  cam_to_world(m, (x - cx) / fx, -((y + 1.f) - cy) / fy, -1.f, dy, ny);
-  float ax = sqrtf(((d0[0] - dx[0]) * (d0[0] - dx[0]) + (d0[1] - dx[1]) * (d0[1] - dx[1])) + (d0[2] - dx[2]) * (d0[2] - dx[2]));
-  float ay = sqrtf(((d0[0] - dy[0]) * (d0[0] - dy[0]) + (d0[1] - dy[1]) * (d0[1] - dy[1])) + (d0[2] - dy[2]) * (d0[2] - dy[2]));
-  float o[3] = {m[3], m[7], m[11]};
+  const PixelRay p = pixel_ray(yi, xi, a.fx[c], a.fy[c], a.cx[c], a.cy[c], a.c2w + c * 12);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { a.origins[(int64_t)r * 3 + k] = o[k]; a.dirs[(int64_t)r * 3 + k] = d0[k]; }
-  a.pixel_area[r] = ax * ay;
-  a.dir_norm[r] = n0;
+  for (int k = 0; k < 3; ++k) { a.origins[(int64_t)r * 3 + k] = p.o[k]; a.dirs[(int64_t)r * 3 + k] = p.d[k]; }
+  a.pixel_area[r] = p.pixel_area;
+  a.dir_norm[r] = p.dir_norm;
   if (a.times) a.times[r] = a.cam_times ? a.cam_times[c] : 0.f;
-  if (a.collide) {
-    float tn = -INFINITY, tf = INFINITY;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float inv = 1.f / (d0[k] + 1e-6f);  // scene_colliders.py:71
-      float t1 = (a.aabb_min[k] - o[k]) * inv, t2 = (a.aabb_max[k] - o[k]) * inv;
-      tn = fmaxf(tn, fminf(t1, t2));
-      tf = fminf(tf, fmaxf(t1, t2));
-    }
-    float np = a.training ? a.near_plane : 0.f;
-    tn = fmaxf(tn, np);
-    tf = fmaxf(tf, tn + 1e-6f);
-    a.nears[r] = tn; a.fars[r] = tf;
-  }
+  if (a.collide) aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, a.training, a.nears[r], a.fars[r]);
 }
 
 // PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77: floor(rand(R,3) * [M,H,W]).long()) fused with the image gather of

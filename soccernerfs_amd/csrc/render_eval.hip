@@ -1,0 +1,229 @@
+// Rendering whole frames (eval / camera paths): ray generation for a pixel range of ONE camera without an index table, and the render tail
+// of the K-Planes model -- plane gather -> sigma_net -> colour net -> get_weights -> RGB / accumulation / depth per ray -- as ONE kernel.
+//
+// Reference: what `ns-render` runs per chunk of --eval-num-rays-per-chunk rays (scripts/render.py:60-131 -> Model.get_outputs_for_camera_ray_bundle,
+// NS/models/base_model.py:159-186): Cameras.generate_rays(camera_indices=k) (NS/cameras/cameras.py:300-418: a meshgrid of image coordinates, then
+// _generate_rays_from_coords :505-741), the AABB collider, and for the nerf level KPlanesField.forward (NS/fields/kplanes_field.py:275-358),
+// RaySamples.get_weights (NS/cameras/rays.py:127-149), RGBRenderer / AccumulationRenderer / DepthRenderer in eval mode
+// (NS/model_components/renderers.py:58-140, :197-223, :226-287; background "last_sample", nan_to_num, clamp).
+//
+// field_render_kernel: the tile of field_fused_common.hpp (the same code field_fwd_kernel runs, so the same density / colour bits) with another
+// work decomposition above it: a workgroup owns a WHOLE RAY and walks its 32-sample tiles front to back.  The ray's density [S], colour [S,3] and
+// bin edges [S+1] stay in LDS (7.7 KB at the limit S = 320, beside the ~43 KB of the tile: two workgroups per CU as before); per-sample density
+// and colour never reach HBM.  After the last tile wave 0 runs the per-ray arithmetic of resample_kernel stage 1 (snerf_weights_fwd) and
+// render_fwd_kernel (training = 0, bg_mode = 1) on the LDS-resident values in the same order (wave_scan_f64, the wave_sum reductions, products
+// rounded one by one), so the outputs equal the three-kernel chain bit for bit -- as ray_train_kernel restates the training step's five.
+//
+// Early ray termination (transmittance_cutoff > 0): after a tile every wave forms the ray's remaining transmittance T = exp(-sum sigma delta) over
+// the samples evaluated so far (the same LDS values, the same arithmetic: the decision is workgroup-uniform without a broadcast).  If T < cutoff
+// the ray's remaining tiles are not gathered or decoded; their samples count as zero density, and the background is the last evaluated sample's
+// colour.  The weights that are dropped sum to less than T: |rgb error| <= cutoff per channel.  cutoff = 0 never terminates: the exact path.
+#include "field_fused_common.hpp"
+#include "raygen_common.hpp"
+
+namespace snerf {
+
+constexpr int RE_MAXS = 320;  // the per-ray kernels' limit (wave_scan_f64: 64 lanes x WSCAN_PER)
+constexpr size_t RAY_LDS_B = sizeof(float) * (RE_MAXS * 6 + 4);  // a ray's density / prefix sums / colour / bin edges behind the tile's LDS plan
+
+struct FrameRaygenArgs {
+  float fx, fy, cx, cy, c2w[12], time;
+  int W, H;
+  int64_t p0, p1;
+  float near_plane, aabb_min[3], aabb_max[3];
+  float* origins; float* dirs; float* pixel_area; float* dir_norm; float* times; float* nears; float* fars;
+};
+
+// pixel p0 + r of the frame in row-major order -> ray r: the (row, col) the meshgrid index table would hold, then raygen_kernel's arithmetic
+__global__ void raygen_frame_kernel(FrameRaygenArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.p1 - a.p0) return;
+  const uint32_t pix = (uint32_t)(a.p0 + r);  // W * H < 2^31 (checked by the entry point)
+  const uint32_t yi = pix / (uint32_t)a.W, xi = pix - yi * (uint32_t)a.W;
+  const PixelRay p = pixel_ray((int64_t)yi, (int64_t)xi, a.fx, a.fy, a.cx, a.cy, a.c2w);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { a.origins[r * 3 + k] = p.o[k]; a.dirs[r * 3 + k] = p.d[k]; }
+  a.pixel_area[r] = p.pixel_area;
+  a.dir_norm[r] = p.dir_norm;
+  if (a.times) a.times[r] = a.time;
+  aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, 0, a.nears[r], a.fars[r]);
+}
+
+struct RayOut {
+  float cutoff;
+  float* rgb_out; float* acc_out; float* depth_median; float* depth_expected;
+  int64_t* median_index; int32_t* samples_done;
+};
+
+// One ray by ONE wavefront from LDS: dd holds the densities of the first `done` samples on entry (the rest count as zero), col the colours,
+// eb the S + 1 euclidean bin edges.  The statements and their order are those of resample_kernel stage 1 and render_fwd_kernel.
+__device__ __forceinline__ void composite_ray(float* dd, float* aux, const float* col, const float* eb, int S, int done, int64_t r, const RayOut& o,
+                                              int lane) {
+#pragma clang fp contract(off)
+  // ---- get_weights (rays.py:127-149) ----
+  for (int i = lane; i < S; i += 64) {
+    const float e0 = eb[i], e1 = eb[i + 1];
+    dd[i] = (e1 - e0) * (i < done ? dd[i] : 0.f);  // delta * sigma
+  }
+  wave_lds_publish();
+  wave_scan_f64<true, false>(dd, aux, S, lane);
+  wave_lds_publish();
+  for (int i = lane; i < S; i += 64) {
+    const float d = dd[i];
+    const float alpha = 1.f - expf(-d);
+    const float T = expf(-aux[i]);
+    dd[i] = nan_to_num(alpha * T);  // from here on dd holds the weights
+  }
+  wave_lds_publish();
+  // ---- compositing, eval mode (renderers.py:113, :133-134, :214, :264-270) ----
+  const float* w = dd;
+  float cr = 0.f, cg = 0.f, cb = 0.f, acc = 0.f, dsum = 0.f;
+  for (int i = lane; i < S; i += 64) {
+    const float wi = w[i];
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (i < done) { x = nan_to_num(col[i * 3]); y = nan_to_num(col[i * 3 + 1]); z = nan_to_num(col[i * 3 + 2]); }
+    cr += wi * x; cg += wi * y; cb += wi * z;
+    acc += wi;
+    const float e0 = eb[i], e1 = eb[i + 1];
+    dsum += wi * ((e0 + e1) / 2.f);
+  }
+  cr = wave_sum(cr); cg = wave_sum(cg); cb = wave_sum(cb); acc = wave_sum(acc); dsum = wave_sum(dsum);
+  // median: first index with cumsum(w) >= 0.5 (searchsorted left), clamped; cumsum by wavefront scan in double
+  wave_scan_f64<false, false>(w, aux, S, lane);
+  wave_lds_publish();
+  int idx = S;
+  for (int i = lane; i < S; i += 64)
+    if (aux[i] >= 0.5f) { idx = i; break; }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int t = __shfl_xor(idx, off, 64); idx = t < idx ? t : idx; }
+  if (idx > S - 1) idx = S - 1;
+  if (lane == 0) {
+    const float* last = col + (done - 1) * 3;  // "last_sample" background: the last EVALUATED sample
+    const float b0 = nan_to_num(last[0]), b1 = nan_to_num(last[1]), b2 = nan_to_num(last[2]);
+    float o0 = cr + b0 * (1.f - acc), o1 = cg + b1 * (1.f - acc), o2 = cb + b2 * (1.f - acc);
+    o0 = fminf(fmaxf(o0, 0.f), 1.f); o1 = fminf(fmaxf(o1, 0.f), 1.f); o2 = fminf(fmaxf(o2, 0.f), 1.f);
+    o.rgb_out[r * 3] = o0; o.rgb_out[r * 3 + 1] = o1; o.rgb_out[r * 3 + 2] = o2;
+    o.acc_out[r] = acc;
+    if (o.median_index) o.median_index[r] = idx;
+    if (o.depth_median) {
+      const float e0 = eb[idx], e1 = eb[idx + 1];
+      o.depth_median[r] = (e0 + e1) / 2.f;
+    }
+    if (o.depth_expected) o.depth_expected[r] = dsum / (acc + 1e-10f);
+    if (o.samples_done) o.samples_done[r] = done;
+  }
+}
+
+// sum of delta * sigma over the tile's 32 samples, the same value in every lane of every wave
+__device__ __forceinline__ float tile_optical_depth(const float* dens, const float* eb, int lane) {
+#pragma clang fp contract(off)
+  float v = 0.f;
+  if (lane < FF_TS) v = (eb[lane + 1] - eb[lane]) * dens[lane];
+  return wave_sum(v);
+}
+
+template <typename T, int NS, bool VD>
+__global__ __launch_bounds__(FF_NW * 64, 4) void field_render_kernel(FieldArgs a, int R, RayOut o) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  float* s_dd = reinterpret_cast<float*>(smem_raw + PlanFF<NS>::BYTES);  // [RE_MAXS] density, then delta * sigma, then the weights
+  float* s_aux = s_dd + RE_MAXS;                                         // [RE_MAXS] the two prefix sums
+  float* s_col = s_aux + RE_MAXS;                                        // [RE_MAXS, 3]
+  float* s_eb = s_col + RE_MAXS * 3;                                     // [RE_MAXS + 1]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int S = a.c.S, n_tiles = S / FF_TS;
+  typename Ops<T>::v8 breg[NS];
+  field_stage_weights<T, NS, VD>(a, smem, breg);
+  for (int ray = blockIdx.x; ray < R; ray += gridDim.x) {
+    // the previous ray's compositing (wave 0) read s_eb: the barrier below is behind it for every wave
+    __syncthreads();
+    for (int i = threadIdx.x; i <= S; i += FF_NW * 64) s_eb[i] = a.c.ebins[(int64_t)ray * (S + 1) + i];
+    float tau = 0.f;
+    int done = S;
+    for (int t = 0; t < n_tiles; ++t) {
+      field_tile<T, NS, 0, VD>(
+          a, (int64_t)ray * S + t * FF_TS, smem, breg, [&](int row, int64_t, float v) { s_dd[t * FF_TS + row] = v; },
+          [&](int row, int64_t, int c, float v) { s_col[(t * FF_TS + row) * 3 + c] = v; });
+      if (o.cutoff > 0.f && t + 1 < n_tiles) {
+        // the tile's densities were published by the barrier behind the sigma_net output layer; s_eb by the tile's first barrier
+        tau += tile_optical_depth(s_dd + t * FF_TS, s_eb + t * FF_TS, lane);
+        if (expf(-tau) < o.cutoff) { done = (t + 1) * FF_TS; break; }  // workgroup-uniform: every wave formed the same tau
+      }
+    }
+    __syncthreads();  // the last tile's colours (waves 0-1) are in LDS
+    if (wave == 0) composite_ray(s_dd, s_aux, s_col, s_eb, S, done, ray, o, lane);
+  }
+}
+
+template <typename T, int NS>
+static int launch_field_render(const FieldArgs& a, int R, const RayOut& o, hipStream_t st, bool vd) {
+  using P = PlanFF<NS>;
+  constexpr size_t BYTES = P::BYTES + RAY_LDS_B;
+  int per_cu = (int)(LDS_LIMIT_B / BYTES);
+  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // two 8-wave workgroups per CU, as field_fwd_kernel
+  int grid = 256 * per_cu;
+  if (grid > R) grid = R;
+  if (vd) {
+    auto k = field_render_kernel<T, NS, true>;
+    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
+  } else {
+    auto k = field_render_kernel<T, NS, false>;
+    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
+  }
+  SNERF_LAUNCH_CHECK("kplanes_field_render");
+  return 0;
+}
+
+static bool render_shape_ok(int S) { return S >= FF_TS && S % FF_TS == 0 && S <= RE_MAXS; }
+
+}  // namespace snerf
+
+using namespace snerf;
+
+extern "C" int snerf_raygen_frame(const snerf_raygen_frame_args* p, snerf_stream_t stream) {
+  SNERF_REQUIRE(p, "raygen_frame: null args");
+  SNERF_REQUIRE(p->W >= 1 && p->H >= 1 && (int64_t)p->W * p->H < (1LL << 31), "raygen_frame: W=%d H=%d", p->W, p->H);
+  SNERF_REQUIRE(p->p0 >= 0 && p->p0 <= p->p1 && p->p1 <= (int64_t)p->W * p->H, "raygen_frame: pixel range [%lld, %lld) outside the %d x %d frame",
+                (long long)p->p0, (long long)p->p1, p->W, p->H);
+  if (p->p0 == p->p1) return 0;
+  SNERF_REQUIRE(p->origins && p->dirs && p->pixel_area && p->dir_norm && p->nears && p->fars, "raygen_frame: null output buffer");
+  FrameRaygenArgs a;
+  a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy; a.time = p->time; a.W = p->W; a.H = p->H; a.p0 = p->p0; a.p1 = p->p1;
+  for (int k = 0; k < 12; ++k) a.c2w[k] = p->c2w[k];
+  a.near_plane = p->near_plane;
+  for (int k = 0; k < 3; ++k) { a.aabb_min[k] = p->aabb_min[k]; a.aabb_max[k] = p->aabb_max[k]; }
+  a.origins = p->origins; a.dirs = p->dirs; a.pixel_area = p->pixel_area; a.dir_norm = p->dir_norm; a.times = p->times; a.nears = p->nears; a.fars = p->fars;
+  hipLaunchKernelGGL(raygen_frame_kernel, dim3(ceil_div(p->p1 - p->p0, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  SNERF_LAUNCH_CHECK("raygen_frame");
+  return 0;
+}
+
+extern "C" int snerf_kplanes_field_render_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* sigma, const snerf_mlp_desc* color, int32_t S) {
+  snerf_coords c = {};
+  c.mode = 1;
+  c.S = S >= 1 ? S : 1;
+  return desc && sigma && color && render_shape_ok(S) && validate_field(desc, &c, 0, sigma, color, 6) == 0 ? 1 : 0;
+}
+
+extern "C" int snerf_kplanes_field_render(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int32_t R,
+                                          const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
+                                          float transmittance_cutoff, float* rgb_out, float* acc_out, float* depth_median, float* depth_expected,
+                                          int64_t* median_index, int32_t* samples_done, snerf_stream_t stream) {
+  SNERF_REQUIRE(coords && R >= 0, "kplanes_field_render: null coords or R=%d", R);
+  SNERF_REQUIRE(coords->mode == 1 && render_shape_ok(coords->S),
+                "kplanes_field_render: needs per-ray coordinates (coords.mode = 1) and S a multiple of %d, <= %d; got mode=%d S=%d", FF_TS, RE_MAXS,
+                coords->mode, coords->S);
+  int rc = validate_field(desc, coords, (int64_t)R * coords->S, sigma, color, 6);
+  if (rc) return rc;
+  SNERF_REQUIRE(transmittance_cutoff >= 0.f && transmittance_cutoff < 1.f, "kplanes_field_render: transmittance_cutoff=%g (0 <= cutoff < 1)",
+                (double)transmittance_cutoff);
+  if (R == 0) return 0;
+  SNERF_REQUIRE(planes && W_sigma && W_color && rgb_out && acc_out, "kplanes_field_render: null buffer");
+  SNERF_REQUIRE(coords->origins && coords->dirs && coords->times && coords->ebins, "kplanes_field_render: null ray buffer");
+  FieldArgs a = {};
+  a.d = *desc; a.planes = planes; a.c = *coords; a.N = (int64_t)R * coords->S; a.Wsig = W_sigma; a.Wcol = W_color;
+  RayOut o = {transmittance_cutoff, rgb_out, acc_out, depth_median, depth_expected, median_index, samples_done};
+  FF_DISPATCH_FWD(launch_field_render, sigma->operands, desc->n_scales, a, R, o, (hipStream_t)stream, color->d_in != FF_GEO);
+}

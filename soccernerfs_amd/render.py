@@ -1,0 +1,263 @@
+"""Rendering whole frames and camera paths from a trained K-Planes model: the `ns-render` / `ns-eval` counterpart on the fused trainer.
+
+What the reference does (scripts/render.py:60-131, scripts/eval.py): per camera Cameras.generate_rays(camera_indices=k), then
+Model.get_outputs_for_camera_ray_bundle (NS/models/base_model.py:159-186) pushes the frame through the model in chunks of
+--eval-num-rays-per-chunk rays and reshapes rgb / accumulation / depth to [H, W, .].  Here a chunk is one fixed sequence of libsnerf launches
+on the caller's stream, built for inference:
+
+  1. snerf_raygen_frame            rays of the chunk's pixels (no index table) + the AABB collider
+  2. snerf_spaced_bins             the first level's bins, no jitter
+  3. 2 x (snerf_kplanes_density_fwd + snerf_pdf_resample, u_mode 2)   the proposal levels, eval-mode sampler
+  4. snerf_kplanes_field_fwd + snerf_weights_fwd + snerf_render_fwd, or (fused_tail=True / a transmittance cutoff) snerf_kplanes_field_render:
+     plane gather -> sigma_net -> colour net -> weights -> rgb / accumulation / median depth in ONE kernel
+
+against ~10 launches per 4096-ray slice through KPlanesTrainer.forward(training=False).  The results are the same bits.
+"""
+import ctypes as C
+import os
+from typing import Dict, Optional, Sequence, Union
+
+import torch
+
+from . import _lib, metrics, ops
+from .camera_paths import get_path_from_json, load_camera_path
+from .cameras import Cameras
+from .fused_step import FusedStep, anneal_value
+
+
+class KPlanesRenderer:
+    """Eval-mode renderer on a KPlanesTrainer's parameters.
+
+    It shares the trainer's parameter views, plane descriptors and net objects (nothing is copied: it renders whatever the trainer holds when a
+    frame is asked for) and owns its own work buffers, sized for `rays_per_chunk`; the trainer's buffers are not touched, so rendering between
+    two training steps leaves training bit-for-bit undisturbed.  Launches go to the CURRENT stream, which must be the stream the trainer's
+    train_step is called on (or be synchronised with it): before its first read of the parameters a frame joins the trainer's pending optimiser
+    sweep with stream waits (KPlanesTrainer._join_prop / _wait_params, the stream-level parts of synchronize()); there is no host synchronise.
+
+    fused_tail=True runs the render tail as one kernel (snerf_kplanes_field_render, the same bits).  It is OFF by default: measured on the trained
+    preset the one kernel takes 25.7 ms of a 960 x 540 frame against 20.6 ms for snerf_kplanes_field_fwd + snerf_weights_fwd + snerf_render_fwd
+    (DESIGN 4.9).  transmittance_cutoff > 0 opts into early ray termination (an approximation bounded by the cutoff) and turns the fused tail
+    on, which it needs.  A shape the render kernel is not built for (S not a multiple of 32, fp32 operands, ...) always runs the unfused tail,
+    with gather + snerf_mlp_fwd where the trainer's own forward uses them."""
+
+    SPACING = FusedStep.SPACING
+    _timing, _timing_all = None, False
+    _FIELD_SLICE = 4096  # rays per launch group of the unfused (fp32-operand) field: bounds the [N, 32 n_scales] feature buffer
+
+    # the launches whose argument lists the fused trainers share (fused_step.py), on this object's buffers
+    _p = FusedStep._p
+    _span = FusedStep._span
+    _spaced_bins = FusedStep._spaced_bins
+    _resample = FusedStep._resample
+    _render_fwd = FusedStep._render_fwd
+    _mlp_fwd = FusedStep._mlp_fwd
+    enable_kernel_timing, disable_kernel_timing, kernel_times_ms = FusedStep.enable_kernel_timing, FusedStep.disable_kernel_timing, FusedStep.kernel_times_ms
+
+    def __init__(self, trainer, rays_per_chunk: int = 65536, transmittance_cutoff: float = 0.0, fused_tail: bool = False):
+        if rays_per_chunk < 1:
+            raise ValueError(f"rays_per_chunk={rays_per_chunk}")
+        if not 0.0 <= transmittance_cutoff < 1.0:
+            raise ValueError(f"transmittance_cutoff={transmittance_cutoff}: expected 0 <= cutoff < 1")
+        self.trainer, self.R, self.dev = trainer, int(rays_per_chunk), trainer.dev
+        self.cfg, self.S, self.aabb, self.lib = trainer.cfg, trainer.S, trainer.aabb, trainer.lib
+        self.transmittance_cutoff = float(transmittance_cutoff)
+        S2 = self.S[2]
+        # a cutoff asks for the fused tail: only that kernel knows a ray's transmittance before its last sample is decoded
+        self.fused_tail = bool((fused_tail or self.transmittance_cutoff > 0.0) and trainer.fused_field and self.lib.snerf_kplanes_field_render_supported(
+            C.byref(trainer._desc_field), C.byref(trainer.sigma_net.desc), C.byref(trainer.color_net.desc), S2))
+        if self.transmittance_cutoff > 0.0 and not self.fused_tail:
+            raise ValueError("transmittance_cutoff > 0 needs the fused render tail (snerf_kplanes_field_render), which is not built for this shape")
+        R = self.R
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
+        self.buf = {"sb": [f(R, s + 1) for s in self.S], "eb": [f(R, s + 1) for s in self.S],
+                    "dens": [f(R, self.S[0]), f(R, self.S[1]), None], "w": [f(R, self.S[0]), f(R, self.S[1]), None]}
+        self._rays = {"origins": f(R, 3), "directions": f(R, 3), "pixel_area": f(R), "directions_norm": f(R), "times": f(R), "nears": f(R), "fars": f(R)}
+        if not self.fused_tail:
+            self.buf["dens"][2], self.buf["w"][2], self.buf["rgb"] = f(R, S2), f(R, S2), f(R * S2, 3)
+            if not trainer.fused_field:
+                n = min(R, self._FIELD_SLICE) * S2
+                self.buf["feat"], self.buf["h"] = f(n, trainer.field_planes.out_dim), f(n, 16)
+                if trainer.view_dependent:
+                    self.buf["cx"] = f(n, 32)
+        if not trainer.fused_proposal:
+            pf = self.cfg.proposal_feature_dim
+            self.buf["pfeat"] = [f(R * self.S[0], pf), f(R * self.S[1], pf)]
+            self.buf["pout"] = [f(R * self.S[0], 1), f(R * self.S[1], 1)]
+        self.samples_done = None   # int32 [H * W] of the last frame when record_samples_done is set (fused tail only)
+        self.record_samples_done = False
+        self.launches = 0          # libsnerf launches issued so far (tools/bench_render.py: launches per frame)
+        self._host_tables = {}
+
+    def _ck(self, rc: int, what: str = ""):
+        self.launches += 1
+        _lib.check(rc, what)
+
+    # ---- cameras ----
+    def _host_table(self, cameras: Cameras):
+        """fx, fy, cx, cy, c2w, times of a camera table as host lists (snerf_raygen_frame takes one camera by value): read back once per table."""
+        key = id(cameras)
+        hit = self._host_tables.get(key)
+        if hit is None or hit[0] is not cameras:
+            t = lambda x: x.detach().cpu().tolist()
+            hit = (cameras, {"fx": t(cameras.fx), "fy": t(cameras.fy), "cx": t(cameras.cx), "cy": t(cameras.cy),
+                             "c2w": t(cameras.camera_to_worlds.reshape(len(cameras), 12)), "times": None if cameras.times is None else t(cameras.times)})
+            self._host_tables = {key: hit}
+        return hit[1]
+
+    def default_anneal(self) -> float:
+        """The proposal-weight annealing exponent tools/train_psnr.py evaluates with: that of the last completed training step."""
+        cfg = self.cfg
+        return anneal_value(max(self.trainer.step - 1, 0), cfg.proposal_weights_anneal_max_num_iters, cfg.proposal_weights_anneal_slope)
+
+    # ---- one chunk ----
+    def _chunk(self, ra: _lib.RaygenFrameArgs, p0: int, p1: int, anneal: float, out: Dict[str, torch.Tensor]):
+        tr, b, rays, lib = self.trainer, self.buf, self._rays, self.lib
+        n = p1 - p0
+        ra.p0, ra.p1 = p0, p1
+        with self._span("raygen_frame"):
+            self._ck(lib.snerf_raygen_frame(C.byref(ra), self._st), "raygen_frame")
+        self.rays, self._fwd_rays = rays, n
+        self._spaced_bins(None)
+        o, d, t = rays["origins"], rays["directions"], rays["times"]
+        for lvl in range(2):
+            co = ops.coords_from_rays(o, d, t, b["eb"][lvl], self.aabb, False)
+            N, net = n * self.S[lvl], tr.prop_nets[lvl]
+            if tr.fused_proposal:
+                with self._span("kplanes_density_fwd"):
+                    self._ck(lib.snerf_kplanes_density_fwd(C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
+                                                           C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]), None, self._st), "kplanes_density_fwd")
+            else:
+                with self._span("kplanes_gather_fwd.prop"):
+                    self._ck(lib.snerf_kplanes_gather_fwd(C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
+                                                          self._p(b["pfeat"][lvl]), self._st), "gather_fwd")
+                self._mlp_fwd(net, b["pfeat"][lvl], self.cfg.proposal_feature_dim, N, b["pout"][lvl], 1, 0, b["dens"][lvl])
+            self._resample(lvl, None, anneal)
+        S2 = self.S[2]
+        co = ops.coords_from_rays(o, d, t, b["eb"][2], self.aabb, True)
+        rgb, acc, depth = out["rgb"][p0:p1], out["accumulation"][p0:p1], out["depth"][p0:p1]
+        if self.fused_tail:
+            sd = self.samples_done[p0:p1] if self.samples_done is not None else None
+            with self._span("kplanes_field_render"):
+                self._ck(lib.snerf_kplanes_field_render(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), n, C.byref(tr.sigma_net.desc),
+                                                        self._p(tr.sigma_net.params), C.byref(tr.color_net.desc), self._p(tr.color_net.params),
+                                                        self.transmittance_cutoff, self._p(rgb), self._p(acc), self._p(depth), None, None,
+                                                        self._p(sd) if sd is not None else None, self._st), "kplanes_field_render")
+            return
+        if tr.fused_field:
+            with self._span("kplanes_field_fwd"):
+                self._ck(lib.snerf_kplanes_field_fwd(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), C.c_int64(n * S2),
+                                                     C.byref(tr.sigma_net.desc), self._p(tr.sigma_net.params), C.byref(tr.color_net.desc),
+                                                     self._p(tr.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]), None, None, None, self._st),
+                         "kplanes_field_fwd")
+        else:  # exact-fp32 operands (or fused_field off): gather + the generic MLP kernels, as the trainer's forward, a slice of rays at a time
+            F = tr.field_planes.out_dim
+            for r0 in range(0, n, self._FIELD_SLICE):
+                r1 = min(r0 + self._FIELD_SLICE, n)
+                N = (r1 - r0) * S2
+                cs = ops.coords_from_rays(o[r0:r1], d[r0:r1], t[r0:r1], b["eb"][2][r0:r1], self.aabb, True)
+                with self._span("kplanes_gather_fwd.field"):
+                    self._ck(lib.snerf_kplanes_gather_fwd(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(cs), C.c_int64(N), self._p(b["feat"]),
+                                                          self._st), "gather_fwd")
+                self._mlp_fwd(tr.sigma_net, b["feat"], F, N, b["h"], 16, 15, b["dens"][2][r0:r1])
+                rgb_s = b["rgb"][r0 * S2:r1 * S2]
+                if tr.view_dependent:
+                    with self._span("kplanes_color_input_fwd"):
+                        self._ck(lib.snerf_kplanes_color_input_fwd(self._p(d[r0:r1]), S2, self._p(b["h"]), C.c_int64(N), self._p(b["cx"]), self._st), "color_input_fwd")
+                    self._mlp_fwd(tr.color_net, b["cx"], 32, N, rgb_s, 3)
+                else:
+                    self._mlp_fwd(tr.color_net, b["h"], 16, N, rgb_s, 3)
+        with self._span("weights_render_fwd"):
+            self._ck(lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), n, S2, self._p(b["w"][2]), self._st), "weights_fwd")
+            b["rgb_out"], b["acc"], b["depth"] = rgb, acc, depth
+            self._render_fwd(False, 1, None, "depth_median")
+
+    # ---- public ----
+    @torch.no_grad()
+    def render_frame(self, cameras: Cameras, index: int, anneal: Optional[float] = None, default_time: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """Camera `index` of `cameras` -> {"rgb": [H,W,3], "accumulation": [H,W,1], "depth": [H,W,1]} (device tensors, fresh per call): the keys and
+        shapes of KPlanesModel.get_outputs_for_camera_ray_bundle; depth is the median depth, as the model renders it.
+        anneal: the proposal sampler's annealing exponent (default: default_anneal()); default_time: the time of a camera table without times."""
+        tab = self._host_table(cameras)
+        if not 0 <= index < len(tab["fx"]):
+            raise IndexError(f"camera index {index} outside the table of {len(tab['fx'])}")
+        if tab["times"] is None and default_time is None:
+            raise ValueError("the cameras carry no times (a camera path has them only if every entry has render_time) and K-Planes is a dynamic "
+                             "model: pass default_time")
+        H, W = cameras.height, cameras.width
+        ra = _lib.RaygenFrameArgs()
+        ra.fx, ra.fy, ra.cx, ra.cy = tab["fx"][index], tab["fy"][index], tab["cx"][index], tab["cy"][index]
+        ra.time = tab["times"][index] if tab["times"] is not None else float(default_time)
+        for k in range(12):
+            ra.c2w[k] = tab["c2w"][index][k]
+        ra.W, ra.H, ra.near_plane = W, H, self.cfg.near_plane
+        for k in range(3):
+            ra.aabb_min[k], ra.aabb_max[k] = self.aabb[0][k], self.aabb[1][k]
+        rays = self._rays
+        ra.origins, ra.dirs, ra.pixel_area, ra.dir_norm = (rays[k].data_ptr() for k in ("origins", "directions", "pixel_area", "directions_norm"))
+        ra.times, ra.nears, ra.fars = rays["times"].data_ptr(), rays["nears"].data_ptr(), rays["fars"].data_ptr()
+        f = lambda c: torch.empty(H * W, c, dtype=torch.float32, device=self.dev)
+        out = {"rgb": f(3), "accumulation": f(1), "depth": f(1)}
+        self.samples_done = torch.empty(H * W, dtype=torch.int32, device=self.dev) if self.record_samples_done and self.fused_tail else None
+        self._st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        # step N's parameters: the proposal chain and the field planes' optimiser sweep (side stream, ping-pong buffers) are joined by stream waits
+        self.trainer._join_prop()
+        self.trainer._wait_params()
+        anneal = self.default_anneal() if anneal is None else float(anneal)
+        for p0 in range(0, H * W, self.R):
+            self._chunk(ra, p0, min(p0 + self.R, H * W), anneal, out)
+        return {k: v.view(H, W, -1) for k, v in out.items()}
+
+    @staticmethod
+    def to_uint8(x: torch.Tensor) -> torch.Tensor:
+        """floor(255 clamp(x, 0, 1) + 0.5) as uint8.  The reference hands the float frame to a third-party image library (mediapy, not in its
+        tree) for this conversion: this one line is RESTATED, not pinned to the reference."""
+        return torch.floor(255.0 * x.clamp(0.0, 1.0) + 0.5).to(torch.uint8)
+
+    @torch.no_grad()
+    def render_camera_path(self, path: Union[str, dict], output_dir: str, outputs: Sequence[str] = ("rgb",), format: str = "png",
+                           default_time: Optional[float] = None, anneal: Optional[float] = None):
+        """Renders every camera of a camera-path dict (or the JSON file holding one) and writes one file per camera, `%05d.png` (or `.npy`: the
+        float frame) in output_dir, named as the reference's `--output-format images` (scripts/render.py:83-85, :131-132).  Several outputs
+        are concatenated along the width, single-channel ones repeated to three channels (:117-130).  Returns the list of files written."""
+        if format not in ("png", "npy"):
+            raise ValueError(f"format={format!r}: 'png' or 'npy' (video encoding is out of scope)")
+        cameras = get_path_from_json(load_camera_path(path))
+        if cameras.times is None and default_time is None:
+            raise ValueError("the camera path has no render_time on every entry and no default_time was given: K-Planes needs a time per frame")
+        os.makedirs(output_dir, exist_ok=True)
+        files = []
+        for k in range(len(cameras)):
+            frame = self.render_frame(cameras, k, anneal=anneal, default_time=default_time)
+            parts = []
+            for name in outputs:
+                if name not in frame:
+                    raise KeyError(f"could not find {name!r} in the model outputs {sorted(frame)}")
+                img = frame[name]
+                parts.append(img.expand(-1, -1, 3) if img.shape[-1] == 1 else img)
+            image = torch.cat(parts, dim=1)
+            fn = os.path.join(output_dir, f"{k:05d}.{format}")
+            if format == "png":
+                from PIL import Image
+
+                Image.fromarray(self.to_uint8(image).cpu().numpy()).save(fn)
+            else:
+                import numpy as np
+
+                np.save(fn, image.cpu().numpy())
+            files.append(fn)
+        return files
+
+    @torch.no_grad()
+    def evaluate(self, cameras: Cameras, images: torch.Tensor, indices: Sequence[int], anneal: Optional[float] = None) -> Dict[str, object]:
+        """PSNR and SSIM of full-frame renders against images[indices] (uint8 [M,H,W,3], or float in [0,1]), per image and averaged, as
+        get_image_metrics_and_images reports them (NS/models/kplanes.py:454-498; soccernerfs_amd/metrics.py)."""
+        psnrs, ssims = [], []
+        for m in indices:
+            rgb = self.render_frame(cameras, int(m), anneal=anneal)["rgb"]
+            gt = images[m].to(self.dev)
+            gt = gt.float() / 255.0 if gt.dtype == torch.uint8 else gt.float()
+            chw = lambda x: x.permute(2, 0, 1)[None]
+            psnrs.append(float(metrics.psnr(rgb, gt)))
+            ssims.append(float(metrics.structural_similarity_index_measure(chw(gt), chw(rgb))))
+        mean = lambda xs: sum(xs) / max(len(xs), 1)
+        return {"psnr": mean(psnrs), "ssim": mean(ssims), "psnr_per_image": psnrs, "ssim_per_image": ssims}

@@ -268,7 +268,7 @@ def test_trainer_depth_supervision_matches_oracle():
     assert "depth_loss" in got
 
 
-@pytest.mark.parametrize("R,S", [(37, 64), (5, 48), (130, 320), (4, 1)])
+@pytest.mark.parametrize("R,S", [(37, 64), (5, 48), (130, 320), (4, 1), (3, 63), (2, 65), (1, 319), (133, 48), (4098, 64)])
 def test_ray_train_kernel_equals_the_five_kernels(R, S):
     """snerf_ray_train_fwd_bwd (the fused trainer's one launch for the nerf level's per-ray work) against snerf_weights_fwd + snerf_render_fwd +
     snerf_render_mse_bwd + snerf_distortion(accumulate) + snerf_weights_bwd run one after the other: every output bit for bit, including rays

@@ -655,8 +655,8 @@ typedef struct {
 /* Host arithmetic only.  tile_rows_log2 <= 0: the largest tile that lets two workgroups share a CU's LDS; first_tiled_level < 0: levels with fewer than
  * 2^16 rows stay atomic. */
 int snerf_tgrid_tile_plan_make(const snerf_tgrid_desc* desc, int64_t B, int32_t tile_rows_log2, int32_t first_tiled_level, snerf_tgrid_tile_plan* plan);
-/* counts [count_ints] and tile_base [n_tiles + 3] are workspaces (no initialisation needed: n_tiles + 1 prefix sums, then two words the fused tile pass
- * uses to hand out tiles); records [record_capacity]; pos4 [B,4] (16-byte aligned)
+/* counts [count_ints] and tile_base [n_tiles + 1] are workspaces (no initialisation needed; the passes touch exactly the n_tiles + 1 prefix
+ * sums, so a longer buffer, such as n_tiles + 3, stays valid); records [record_capacity]; pos4 [B,4] (16-byte aligned)
  * receives (x, y, z, time) per sample -- the later passes read ONLY pos4, grad_out, tile_base and records, never `coords`, so they may run on another
  * stream while the caller's ray buffers are rewritten.  grad_out may be NULL: the pass then files every in-range sample (it depends on the sample positions
  * only, so it can run as soon as those exist -- beside the forward); with grad_out, (sample, level) pairs whose gradient is all zero are left out.  B < 2^28. */

@@ -3,7 +3,7 @@
 // sample position of snerf_coords.  Everything here is evaluated exactly as written (no contraction): the kernels of both files must land in the
 // same cell for the same sample.
 #pragma once
-#include "common.hpp"
+#include "table_level.hpp"
 
 #pragma clang fp contract(off)
 
@@ -25,18 +25,7 @@ __device__ __forceinline__ void tg_slot_from_time(float t, int C, int n_rows, in
   }
 }
 
-// One level of a D = 3 grid: table rows [off0, off0 + rows), position scale, and the per-axis multipliers whose XOR (hashed level) or sum
-// (dense level) over the corner's integer coordinates, reduced modulo `rows`, is get_grid_index (.cu:62-88).
-struct TgLevel {
-  uint32_t off0, rows, mult[3];
-  float scale;
-  bool hashed, pow2;
-  __device__ __forceinline__ uint32_t row_of(uint32_t cx, uint32_t cy, uint32_t cz) const {
-    const uint32_t a = cx * mult[0], b = cy * mult[1], c = cz * mult[2];
-    const uint32_t index = hashed ? (a ^ b ^ c) : (a + b + c);
-    return pow2 ? (index & (rows - 1u)) : (index % rows);
-  }
-};
+using TgLevel = TableLevel;  // table_level.hpp: shared with the static hash grid's tiled backward
 
 __device__ __forceinline__ TgLevel tg_level(const snerf_tgrid_desc& d, int level) {
   TgLevel lv;

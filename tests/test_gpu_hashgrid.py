@@ -242,10 +242,13 @@ def test_full_nerfplayer_preset_trains():
     (dict(n_levels=3, n_features_per_level=4, base_resolution=4, per_level_scale=2.0, log2_hashmap_size=12), 4, 0),                   # all dense
     (dict(n_levels=5, n_features_per_level=8, base_resolution=5, per_level_scale=1.5, log2_hashmap_size=9), 3, 1),
     (dict(n_levels=4, n_features_per_level=1, base_resolution=7, per_level_scale=1.6, log2_hashmap_size=11), 5, 2),
+    (dict(n_levels=4, n_features_per_level=1, base_resolution=7, per_level_scale=1.6, log2_hashmap_size=11), 5, 4),                   # empty plan: every level atomic
 ])
 def test_tiled_table_backward_equals_the_atomic_kernel_and_its_fused_adam_equals_scatter_then_adam(cfg, sh, lc):
     """csrc/hashgrid_tiles.hip (round 6, ABI 14): the owner-computes table backward against hashgrid_kernel's atomic scatter (itself pinned against the oracle's
-    autograd above) -- same entries, summation-order accuracy, ACCUMULATING -- and its fused Adam form against scatter -> snerf_adam_step over three steps."""
+    autograd above) -- same entries, summation-order accuracy, ACCUMULATING -- and its fused Adam form against scatter -> snerf_adam_step over three steps.
+    The all-dense case runs with sentinel words behind tile_base[n_tiles] (callers allocate exactly n_tiles + 1); with first_tiled_level = n_levels the binning
+    takes its "empty" branch and the tile passes add nothing to what the atomic kernel did."""
     import ctypes as C
 
     from soccernerfs_amd import _lib, ops
@@ -255,6 +258,14 @@ def test_tiled_table_backward_equals_the_atomic_kernel_and_its_fused_adam_equals
     enc = Encoding(3, {"otype": "HashGrid", **cfg}).to(DEV)
     F = cfg["n_features_per_level"]
     L = _lib.lib()
+    guarded, empty = (sh, lc) == (4, 0), lc == cfg["n_levels"]
+
+    def guard_tile_base(tb):
+        n = tb.plan.n_tiles + 1
+        buf = torch.full((n + 8,), -77, dtype=torch.int32, device=DEV)
+        tb.tile_base = buf[:n]
+        return buf
+
     for B in (5000, 1237):
         x = torch.rand(B, 3, generator=gen)
         x[0, 0], x[1, 2], x[2], x[3] = 1.0, 0.0, -0.13, 1.21  # no bounds check in tcnn's grid: wraps / hashes
@@ -265,12 +276,18 @@ def test_tiled_table_backward_equals_the_atomic_kernel_and_its_fused_adam_equals
         _lib.check(L.snerf_hashgrid_encode_bwd(C.byref(enc.desc), None, ops._ptr(x), C.c_int64(B), ops._ptr(gout), ops._ptr(ref), None, ops._stream()))
         tb = TiledHashTableBackward(enc, B, tile_rows_log2=sh, first_tiled_level=lc)
         assert tb.plan.n_tiles == tb.plan.tile_start[cfg["n_levels"]] and (sh == 0 or tb.plan.tile_rows_log2 == sh) and tb.plan.first_tiled_level == lc
+        guard = guard_tile_base(tb) if guarded else None
         got = torch.zeros_like(ref)
         tb.bin(x, gout)
         tb.coarse_levels(x, gout, got)
+        coarse_only = got.clone()
         tb.scatter(x, gout, got)
         torch.cuda.synchronize()
-        assert 0 < int(tb.tile_base[-1]) <= tb.plan.record_capacity
+        if empty:
+            assert int(tb.tile_base[-1]) == 0 and torch.equal(got, coarse_only)
+        else:
+            assert 0 < int(tb.tile_base[-1]) <= tb.plan.record_capacity
+        assert guard is None or bool((guard[-8:] == -77).all())
         scale = float(ref.abs().max())
         torch.testing.assert_close(got, ref, rtol=1e-5, atol=2e-6 * scale)
         assert bool(((got != 0) == (ref != 0)).all())
@@ -283,6 +300,7 @@ def test_tiled_table_backward_equals_the_atomic_kernel_and_its_fused_adam_equals
     m_ref, v_ref, m_new, v_new, g_ref, g_new = z(), z(), z(), z(), z(), z()
     B = 3000
     tb = TiledHashTableBackward(enc, B, tile_rows_log2=sh, first_tiled_level=lc)
+    guard = guard_tile_base(tb) if guarded else None
     for step in range(1, 4):
         x = torch.rand(B, 3, generator=gen).to(DEV)
         gout = ((torch.rand(B, cfg["n_levels"] * F, generator=gen) - 0.5) * 1e-3).to(DEV)
@@ -293,6 +311,8 @@ def test_tiled_table_backward_equals_the_atomic_kernel_and_its_fused_adam_equals
         tb.scatter_adam(x, gout, g_new if lc > 0 else None, p_new, m_new, v_new, 1e-2, step, 1e-6)
         torch.cuda.synchronize()
         assert float(g_new.abs().max()) == 0.0  # the coarse levels' gradient was read AND cleared
+        assert guard is None or bool((guard[-8:] == -77).all())
+        assert not empty or int(tb.tile_base[-1]) == 0
         torch.testing.assert_close(m_new, m_ref, rtol=1e-4, atol=1e-9)
         torch.testing.assert_close(v_new, v_ref, rtol=2e-4, atol=1e-15)
         assert float(((p_new - p_ref).abs() > 1e-5).float().mean()) < 1e-4

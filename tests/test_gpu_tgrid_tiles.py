@@ -54,8 +54,25 @@ CASES = [
 ]
 
 
+# CASES[3] once more with every level atomic (first_tiled_level = L): the binning takes its "empty" branch and the tile pass holds no record
+EMPTY_PLAN = (CASES[3][0], CASES[3][1], 4)
+GUARD = 8  # sentinel ints behind tile_base[n_tiles]
+
+
+def _guard_tile_base(tb):
+    """tb.tile_base becomes the first n_tiles + 1 ints of a buffer with GUARD sentinels behind them (the passes own [n_tiles + 1] and not a word more)."""
+    n = tb.plan.n_tiles + 1
+    buf = torch.full((n + GUARD,), -77, dtype=torch.int32, device=DEV)
+    tb.tile_base = buf[:n]
+    return buf
+
+
+def _assert_guard_intact(buf):
+    assert bool((buf[-GUARD:] == -77).all()), buf[-GUARD:].tolist()
+
+
 @pytest.mark.parametrize("mode", ["rays", "points"])
-@pytest.mark.parametrize("kw,sh,lc", CASES)
+@pytest.mark.parametrize("kw,sh,lc", CASES + [EMPTY_PLAN])
 def test_tiled_scatter_equals_the_per_sample_atomic_kernel(kw, sh, lc, mode):
     from soccernerfs_amd.temporal_grid import TemporalGridEncoder, TiledTableBackward
 
@@ -70,11 +87,19 @@ def test_tiled_scatter_equals_the_per_sample_atomic_kernel(kw, sh, lc, mode):
         ref = _per_sample_bwd(enc, co, times, S, B, gout)
         tb = TiledTableBackward(enc, B, tile_rows_log2=sh, first_tiled_level=lc)
         assert tb.plan.n_tiles == tb.plan.tile_start[enc.num_levels] and (sh == 0 or tb.plan.tile_rows_log2 == sh)
+        guard = _guard_tile_base(tb) if (kw, sh, lc) == CASES[3] else None
         got = torch.zeros_like(ref)
         tb.bin(co, times, S, gout)
         tb.coarse_levels(co, times, S, gout, got)
-        tb.scatter(gout, got)
+        if lc == enc.num_levels:  # empty plan: the atomic kernel has done all of it, and the tile pass leaves that unchanged
+            coarse_only = got.clone()
+            tb.scatter(gout, got)
+            assert int(tb.tile_base[tb.plan.n_tiles]) == 0 and torch.equal(got, coarse_only)
+        else:
+            tb.scatter(gout, got)
         torch.cuda.synchronize()
+        if guard is not None:
+            _assert_guard_intact(guard)
         n_rec = int(tb.tile_base[tb.plan.n_tiles])
         assert n_rec <= tb.plan.record_capacity and (n_rec > 0) == (tb.plan.first_tiled_level < enc.num_levels)
         scale = float(ref.abs().max())
@@ -90,15 +115,12 @@ def test_tiled_scatter_equals_the_per_sample_atomic_kernel(kw, sh, lc, mode):
         torch.testing.assert_close(again, 2 * ref, rtol=1e-5, atol=4e-6 * scale)
 
 
-@pytest.mark.parametrize("ws", ["1", "0"])
 @pytest.mark.parametrize("tv", [False, True])
-@pytest.mark.parametrize("kw,sh,lc", CASES[:4])
-def test_fused_adam_equals_scatter_then_tv_then_adam(kw, sh, lc, tv, ws, monkeypatch):
-    """ws = 0 (default): one workgroup per tile; ws = 1: the persistent, wave-specialised tile kernel (builder waves sum tile k + 1 while streamer waves run Adam over tile k; tiles handed out by a
-    ticket); ws = 0: one workgroup per tile (SNERF_TGRID_TILES_WS=0).  Three optimiser steps, so the ticket words are reused across launches."""
+@pytest.mark.parametrize("kw,sh,lc", CASES[:4] + [EMPTY_PLAN])
+def test_fused_adam_equals_scatter_then_tv_then_adam(kw, sh, lc, tv):
+    """One workgroup per tile (tt_tiles_kernel<C, 1>), three optimiser steps.  CASES[3] runs with sentinel words behind tile_base[n_tiles]; EMPTY_PLAN has
+    no tiled level, so the fused pass is Adam over what the atomic kernel left in the gradient buffer."""
     from soccernerfs_amd import _lib, ops
-
-    monkeypatch.setenv("SNERF_TGRID_TILES_WS", ws)
     from soccernerfs_amd.temporal_grid import TemporalGridEncoder, TiledTableBackward
 
     gen = torch.Generator().manual_seed(9)
@@ -114,6 +136,7 @@ def test_fused_adam_equals_scatter_then_tv_then_adam(kw, sh, lc, tv, ws, monkeyp
     m_ref, v_ref, m_new, v_new, g_ref, g_new = z(), z(), z(), z(), z(), z()
     srow, part = torch.zeros(rows, device=DEV), torch.zeros(64, 16, device=DEV)
     tb = TiledTableBackward(enc, B, tile_rows_log2=sh, first_tiled_level=lc)
+    guard = _guard_tile_base(tb) if (kw, sh, lc) == CASES[3] else None
     lr, eps = 1e-2, 1e-12
     for step in range(1, 4):
         co, times, keep = _batch(gen, R, S, "rays")
@@ -134,6 +157,10 @@ def test_fused_adam_equals_scatter_then_tv_then_adam(kw, sh, lc, tv, ws, monkeyp
         tb.coarse_levels(co, times, S, gout, g_new)
         tb.scatter_adam(gout, g_new, p_new, m_new, v_new, lr, step, eps, tv_cols=(ca, cb) if tv else None, srow=srow if tv else None)
         torch.cuda.synchronize()
+        if guard is not None:
+            _assert_guard_intact(guard)
+        if lc == enc.num_levels:
+            assert int(tb.tile_base[tb.plan.n_tiles]) == 0
         assert float(g_new.abs().max()) == 0.0 and float(g_ref.abs().max()) == 0.0  # both leave a cleared gradient buffer
         # Adam's first steps move a parameter by ~lr whatever the gradient's size, so an element whose tiny gradient differs in its last bits (another
         # summation order) may move differently: compare moments tightly, parameters on all but a vanishing fraction of elements

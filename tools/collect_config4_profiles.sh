@@ -60,7 +60,7 @@ R, P = line["rays"], line["params"]
 ms = lambda pat: sum(float(r["TotalDurationNs"]) for r in rows if pat in r["Name"]) / steps / 1e6
 tr = lambda pat: sum(v for k, v in per_step.items() if pat in k)
 adam_ms = ms("adam_tv_kernel") + ms("adam_kernel")
-tiles_ms, bin_ms = ms("tt_tiles_kernel"), ms("tt_bin_kernel") + ms("tt_scan_") + ms("tt_positions_kernel")
+tiles_ms, bin_ms = ms("tt_tiles_kernel"), ms("tile_bin_kernel") + ms("tile_scan_") + ms("tt_positions_kernel")
 fwd_ms, bwd_ms = ms("tgrid_kernel<false") + ms("tgrid_fwd_runs_kernel"), ms("tgrid_kernel<true") + ms("tgrid_bwd_runs_kernel")
 alg_ray, sec_ray = 242688, 256 * 40 * 64 + 96 * 40 * 64 + 48 * 128 * 64  # algorithmic bytes / 64-B sectors touched per ray, forward
 line["roofline"] = {
@@ -84,7 +84,7 @@ if tiles_ms > 0:
     line["roofline_tiles"] = {"bound": "hbm", "kernel": "tt_tiles_kernel<2,1>: gradient scatter (LDS, one owner per 256-row tile) + temporal TV + Adam of the main table in one pass",
                               "achieved": 24 * n_main / (tiles_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": 24 * n_main / (tiles_ms * 1e-3) / 1e9 / 8000.0,
                               "algorithmic_per_step": 24 * n_main, "kernel_ms_per_step": tiles_ms, "traffic": tr("tt_tiles_kernel"),
-                              "binning_ms_per_step": bin_ms, "binning_traffic": tr("tt_bin_kernel") + tr("tt_scan_") + tr("tt_positions_kernel")}
+                              "binning_ms_per_step": bin_ms, "binning_traffic": tr("tile_bin_kernel") + tr("tile_scan_") + tr("tt_positions_kernel")}
 json.dump(line, open(f"{out}/{tag}_nerfplayer_fused_bench.json", "w"), indent=1)
 print(json.dumps(line)[:1500])
 PY

@@ -32,8 +32,9 @@ typedef void* snerf_stream_t; /* hipStream_t */
 #define SNERF_MAX_SCALES 8
 #define SNERF_ABI_VERSION 16
 /* Additions that leave every ABI-16 entry point and struct as it was count a REVISION instead of a new version, so that callers pinned to
- * version 16 keep loading.  Revision 1: snerf_raygen_frame, snerf_kplanes_field_render(_supported), snerf_abi_revision itself. */
-#define SNERF_ABI_REVISION 1
+ * version 16 keep loading.  Revision 1: snerf_raygen_frame, snerf_kplanes_field_render(_supported), snerf_abi_revision itself.
+ * Revision 2: snerf_raygen_lens, snerf_raygen_frame_lens (rays through the cameras' OpenCV lens distortion). */
+#define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
 int snerf_abi_version(void);
@@ -566,6 +567,60 @@ typedef struct {
   float* fars;             /* [p1 - p0] */
 } snerf_raygen_frame_args;
 int snerf_raygen_frame(const snerf_raygen_frame_args* args, snerf_stream_t stream);
+
+/* ABI 16 revision 2: snerf_raygen through the cameras' lens distortion, OpenCV coefficients (k1, k2, k3, k4, p1, p2) per camera.
+ * Cameras._generate_rays_from_coords with distortion_params (NS/cameras/cameras.py:620-653): the pixel's normalised coordinates and its two
+ * one-pixel offsets (x + 1, y + 1) are EACH undistorted by radial_and_tangential_undistort (NS/cameras/camera_utils.py:363-401: ten Newton
+ * steps, no early exit, a step of zero where |denominator| <= 1e-3; residual and Jacobian of _compute_residual_and_jacobian :298-360) before
+ * the directions, their norms and the pixel area are formed as in snerf_raygen (:704-741).  The fields are snerf_raygen_args' followed by the
+ * table: distortion_stride 6 = a [M,6] table, one row per camera; 0 = one row [6] shared by all cameras.  With an all-zero row every Newton
+ * step is exactly zero and every output equals snerf_raygen bit for bit.  Perspective cameras only. */
+typedef struct {
+  const int64_t* indices;
+  const float* fx; const float* fy; const float* cx; const float* cy; /* [M] */
+  const float* c2w;        /* [M,3,4] */
+  const float* cam_times;  /* [M] or NULL */
+  int32_t R;
+  int32_t collide;
+  int32_t training;
+  float near_plane;
+  float aabb_min[3];
+  float aabb_max[3];
+  float* origins;          /* [R,3] */
+  float* dirs;             /* [R,3] */
+  float* pixel_area;       /* [R] */
+  float* dir_norm;         /* [R] */
+  float* times;            /* [R] or NULL */
+  float* nears;            /* [R] */
+  float* fars;             /* [R] */
+  const float* distortion; /* [M,6] (stride 6) or [6] (stride 0) */
+  int32_t distortion_stride;
+} snerf_raygen_lens_args;
+int snerf_raygen_lens(const snerf_raygen_lens_args* args, snerf_stream_t stream);
+
+/* ABI 16 revision 2: snerf_raygen_frame through ONE camera's lens distortion (NS/cameras/cameras.py:620-653, NS/cameras/camera_utils.py:298-401,
+ * as snerf_raygen_lens): the fields of snerf_raygen_frame_args followed by the camera's row (k1, k2, k3, k4, p1, p2).  Every output equals
+ * snerf_raygen_lens on the meshgrid index table bit for bit, and snerf_raygen_frame when the row is all zero. */
+typedef struct {
+  float fx, fy, cx, cy;
+  float c2w[12];           /* [3,4] row-major */
+  float time;
+  int32_t W, H;
+  int32_t _pad;
+  int64_t p0, p1;
+  float near_plane;
+  float aabb_min[3];
+  float aabb_max[3];
+  float* origins;          /* [p1 - p0, 3] */
+  float* dirs;             /* [p1 - p0, 3] */
+  float* pixel_area;       /* [p1 - p0] */
+  float* dir_norm;         /* [p1 - p0] */
+  float* times;            /* [p1 - p0] or NULL */
+  float* nears;            /* [p1 - p0] */
+  float* fars;             /* [p1 - p0] */
+  float distortion[6];
+} snerf_raygen_frame_lens_args;
+int snerf_raygen_frame_lens(const snerf_raygen_frame_lens_args* args, snerf_stream_t stream);
 
 /* PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77): indices[R,3] = floor(u[R,3] * (M,H,W)) as int64 (image, row, col), fused
  * with collate_image_dataset_batch's gather (:111-123): target[R,3] = images[c,y,x,:] / 255 for a resident uint8 image cache

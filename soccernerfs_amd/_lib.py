@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_PKG, "libsnerf.so")
 
 MAX_SCALES = 8
 ABI_VERSION = 16
-ABI_REVISION = 1  # additions on top of ABI 16 (include/snerf.h: SNERF_ABI_REVISION)
+ABI_REVISION = 2  # additions on top of ABI 16 (include/snerf.h: SNERF_ABI_REVISION)
 
 
 class KPlanesDesc(C.Structure):
@@ -100,6 +100,16 @@ class RaygenFrameArgs(C.Structure):
                 ("times", C.c_void_p), ("nears", C.c_void_p), ("fars", C.c_void_p)]
 
 
+class RaygenLensArgs(C.Structure):
+    """snerf_raygen_lens_args (ABI 16 revision 2, csrc/raygen.hip): RaygenArgs' fields, then the distortion table and its stride (6 or 0)."""
+    _fields_ = RaygenArgs._fields_ + [("distortion", C.c_void_p), ("distortion_stride", C.c_int32)]
+
+
+class RaygenFrameLensArgs(C.Structure):
+    """snerf_raygen_frame_lens_args (ABI 16 revision 2, csrc/render_eval.hip): RaygenFrameArgs' fields, then the camera's k1 k2 k3 k4 p1 p2."""
+    _fields_ = RaygenFrameArgs._fields_ + [("distortion", C.c_float * 6)]
+
+
 class TgridDesc(C.Structure):
     _fields_ = [("D", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("grid_C", C.c_int32), ("H", C.c_int32), ("gridtype", C.c_int32),
                 ("align_corners", C.c_int32), ("S", C.c_float), ("offsets", C.c_int32 * 33)]
@@ -183,6 +193,8 @@ def lib():
     l.snerf_isg_maps.argtypes = [P, I, I, I, I, I, P, P, P, I, F, P, P, P]
     l.snerf_ist_maps.argtypes = [P, I, I, I, I, P, P, F, P, P]
     l.snerf_kplanes_field_render.argtypes = [P, P, P, I, P, P, P, P, F, P, P, P, P, P, P, P]
+    l.snerf_raygen_lens.argtypes = [P, P]
+    l.snerf_raygen_frame_lens.argtypes = [P, P]
     if l.snerf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
     revision = l.snerf_abi_revision() if hasattr(l, "snerf_abi_revision") else 0  # a library from before revisions were counted
@@ -241,6 +253,8 @@ EXPORTS = [
     "snerf_kplanes_scatter_sorted_scales",
     "snerf_raygen",
     "snerf_raygen_frame",
+    "snerf_raygen_lens",
+    "snerf_raygen_frame_lens",
     "snerf_aabb_collide",
     "snerf_tgrid_encode_fwd",
     "snerf_hashgrid_layout",

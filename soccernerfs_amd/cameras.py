@@ -1,5 +1,11 @@
-"""Pinhole camera table + RayGenerator with the interface of NS/cameras/cameras.py (perspective, no distortion slice)
-and NS/model_components/ray_generators.py."""
+"""Perspective camera table + RayGenerator with the interface of NS/cameras/cameras.py and NS/model_components/ray_generators.py.
+
+distortion_params [M,6] (or [6]) are the OpenCV coefficients k1 k2 k3 k4 p1 p2 the dataparsers read.  A table with a non-zero coefficient
+generates its rays through the lens, as the reference does (cameras.py:635-653: every pixel coordinate and its two one-pixel offsets are
+undistorted with ten Newton steps; ops.generate_rays(distortion_params=...) -> snerf_raygen_lens); a table without coefficients, or with
+all-zero rows (for which the undistortion is the identity), takes the pinhole kernel.  Fisheye and equirectangular cameras and the camera
+optimiser's distortion_params_delta are not built."""
+import copy
 from typing import Optional
 
 import torch
@@ -21,7 +27,14 @@ class Cameras:
         self.width, self.height = int(width), int(height)
         self.times = None if times is None else times.reshape(-1).float().to(dev).contiguous()
         self.ids = kwargs.get("ids")  # camera uid per image (Broadcast-style parser), carried for the samplers / metrics
-        self.distortion_params = kwargs.get("distortion_params")  # carried only: rays are generated for the pinhole model
+        dp = kwargs.get("distortion_params")
+        if dp is not None:
+            dp = torch.as_tensor(dp).float()
+            if dp.dim() == 0 or dp.shape[-1] != 6 or dp.numel() not in (6, 6 * M):
+                raise ValueError(f"distortion_params {tuple(dp.shape)}: expected [6] or [{M}, 6] (k1 k2 k3 k4 p1 p2)")
+        # decided once, here, on the host: generate_rays must not read the device back to choose its kernel (.to() copies the flag)
+        self.has_distortion = bool(dp is not None and bool((dp != 0).any()))
+        self.distortion_params = None if dp is None else dp.reshape(-1, 6).to(dev).expand(M, 6).contiguous()
 
     def rescale_output_resolution(self, scaling_factor: float) -> None:
         """NS/cameras/cameras.py:792-816."""
@@ -34,13 +47,17 @@ class Cameras:
         return self.camera_to_worlds.shape[0]
 
     def to(self, device):
-        return Cameras(self.camera_to_worlds.to(device), self.fx.to(device), self.fy.to(device), self.cx.to(device), self.cy.to(device),
-                       self.width, self.height, None if self.times is None else self.times.to(device), ids=self.ids,
-                       distortion_params=self.distortion_params)
+        """The same table on `device`.  A copy of this object with its tensors moved: the host flag goes along, nothing is read back."""
+        moved = copy.copy(self)
+        for name in ("camera_to_worlds", "fx", "fy", "cx", "cy", "times", "distortion_params"):
+            t = getattr(self, name)
+            setattr(moved, name, None if t is None else t.to(device))
+        return moved
 
     def generate_rays(self, camera_indices: torch.Tensor, coords: Optional[torch.Tensor] = None, aabb=None, near_plane=0.0,
-                      training=True, **kwargs) -> RayBundle:
-        """camera_indices [R,1] (or an int for a full image); coords [R,2] = (y+0.5, x+0.5) pixel centres."""
+                      training=True, disable_distortion: bool = False, **kwargs) -> RayBundle:
+        """camera_indices [R,1] (or an int for a full image); coords [R,2] = (y+0.5, x+0.5) pixel centres.
+        disable_distortion (cameras.py:300-311): pinhole rays even for a table that carries non-zero distortion coefficients."""
         if isinstance(camera_indices, int):
             ys, xs = torch.meshgrid(torch.arange(self.height), torch.arange(self.width), indexing="ij")
             idx = torch.stack([torch.full_like(ys, camera_indices), ys, xs], -1).reshape(-1, 3).to(self.camera_to_worlds.device)
@@ -49,7 +66,8 @@ class Cameras:
             yx = torch.floor(coords).long()
             idx = torch.cat([camera_indices.reshape(-1, 1).long(), yx], dim=-1)
             shape = None
-        out = ops.generate_rays(idx.contiguous(), self.fx, self.fy, self.cx, self.cy, self.camera_to_worlds, self.times, aabb, near_plane, training)
+        out = ops.generate_rays(idx.contiguous(), self.fx, self.fy, self.cx, self.cy, self.camera_to_worlds, self.times, aabb, near_plane, training,
+                                distortion_params=self.distortion_params if self.has_distortion and not disable_distortion else None)
         rb = RayBundle(origins=out["origins"], directions=out["directions"], pixel_area=out["pixel_area"], camera_indices=out["camera_indices"],
                        nears=out.get("nears"), fars=out.get("fars"), metadata={"directions_norm": out["directions_norm"]},
                        times=out["times"] if self.times is not None else None)

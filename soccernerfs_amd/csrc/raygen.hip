@@ -1,4 +1,4 @@
-// Ray generation (pinhole, no distortion, camera optimiser off) fused with the AABB collider.
+// Ray generation (pinhole, or through the OpenCV lens distortion; camera optimiser off) fused with the AABB collider.
 //
 // Reference: RayGenerator.forward (NS/model_components/ray_generators.py:41-59) ->
 // Cameras._generate_rays_from_coords (NS/cameras/cameras.py:505-741; the perspective slice :596-633,:663-670,
@@ -31,6 +31,31 @@ __global__ void raygen_kernel(RaygenArgs a) {
   const PixelRay p = pixel_ray(yi, xi, a.fx[c], a.fy[c], a.cx[c], a.cy[c], a.c2w + c * 12);
 #pragma unroll
   for (int k = 0; k < 3; ++k) { a.origins[(int64_t)r * 3 + k] = p.o[k]; a.dirs[(int64_t)r * 3 + k] = p.d[k]; }
+  a.pixel_area[r] = p.pixel_area;
+  a.dir_norm[r] = p.dir_norm;
+  if (a.times) a.times[r] = a.cam_times ? a.cam_times[c] : 0.f;
+  if (a.collide) aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, a.training, a.nears[r], a.fars[r]);
+}
+
+// raygen_kernel through the cameras' lens distortion (Cameras._generate_rays_from_coords with distortion_params, cameras.py:635-653): a sibling
+// kernel, so that the pinhole kernel above is the code it always was.  distortion: [M,6] rows (stride 6) or one row for all cameras (stride 0).
+struct RaygenLensArgs {
+  RaygenArgs base;
+  const float* distortion;
+  int distortion_stride;
+};
+
+__global__ void raygen_lens_kernel(RaygenLensArgs l) {
+  const RaygenArgs& a = l.base;
+  int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.R) return;
+  const int64_t c = a.indices[(int64_t)r * 3], yi = a.indices[(int64_t)r * 3 + 1], xi = a.indices[(int64_t)r * 3 + 2];
+  float k[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) k[i] = l.distortion[c * l.distortion_stride + i];
+  const PixelRay p = pixel_ray_lens(yi, xi, a.fx[c], a.fy[c], a.cx[c], a.cy[c], a.c2w + c * 12, k);
+#pragma unroll
+  for (int k3 = 0; k3 < 3; ++k3) { a.origins[(int64_t)r * 3 + k3] = p.o[k3]; a.dirs[(int64_t)r * 3 + k3] = p.d[k3]; }
   a.pixel_area[r] = p.pixel_area;
   a.dir_norm[r] = p.dir_norm;
   if (a.times) a.times[r] = a.cam_times ? a.cam_times[c] : 0.f;
@@ -124,6 +149,28 @@ extern "C" int snerf_raygen(const snerf_raygen_args* p, snerf_stream_t stream) {
   a.nears = p->nears; a.fars = p->fars;
   hipLaunchKernelGGL(raygen_kernel, dim3(ceil_div(p->R, 256)), dim3(256), 0, (hipStream_t)stream, a);
   SNERF_LAUNCH_CHECK("raygen");
+  return 0;
+}
+
+extern "C" int snerf_raygen_lens(const snerf_raygen_lens_args* p, snerf_stream_t stream) {
+  SNERF_REQUIRE(p, "raygen_lens: null args");
+  SNERF_REQUIRE(p->R >= 0, "raygen_lens: R=%d", p->R);
+  SNERF_REQUIRE(p->distortion_stride == 0 || p->distortion_stride == 6, "raygen_lens: distortion_stride=%d (0: one shared row, 6: a [M,6] table)",
+                p->distortion_stride);
+  if (p->R == 0) return 0;
+  SNERF_REQUIRE(p->indices && p->fx && p->fy && p->cx && p->cy && p->c2w && p->distortion, "raygen_lens: null camera/index/distortion buffer");
+  SNERF_REQUIRE(p->origins && p->dirs && p->pixel_area && p->dir_norm, "raygen_lens: null output buffer");
+  SNERF_REQUIRE(!p->collide || (p->nears && p->fars), "raygen_lens: collide set but nears/fars null");
+  RaygenLensArgs l;
+  RaygenArgs& a = l.base;
+  a.indices = p->indices; a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy; a.c2w = p->c2w; a.cam_times = p->cam_times; a.R = p->R;
+  a.origins = p->origins; a.dirs = p->dirs; a.pixel_area = p->pixel_area; a.dir_norm = p->dir_norm; a.times = p->times;
+  a.collide = p->collide; a.training = p->training; a.near_plane = p->near_plane;
+  for (int k = 0; k < 3; ++k) { a.aabb_min[k] = p->aabb_min[k]; a.aabb_max[k] = p->aabb_max[k]; }
+  a.nears = p->nears; a.fars = p->fars;
+  l.distortion = p->distortion; l.distortion_stride = p->distortion_stride;
+  hipLaunchKernelGGL(raygen_lens_kernel, dim3(ceil_div(p->R, 256)), dim3(256), 0, (hipStream_t)stream, l);
+  SNERF_LAUNCH_CHECK("raygen_lens");
   return 0;
 }
 

@@ -1,4 +1,4 @@
-// One pixel's ray (pinhole, no distortion) and its AABB interval: the arithmetic of Cameras._generate_rays_from_coords (NS/cameras/cameras.py:596-633,
+// One pixel's ray (pinhole, or through an OpenCV lens) and its AABB interval: the arithmetic of Cameras._generate_rays_from_coords (NS/cameras/cameras.py:596-633,
 // :663-670, :704-741) and AABBBoxCollider._intersect_with_aabb (NS/model_components/scene_colliders.py:59-95), shared by the kernel that reads
 // (camera, row, col) from an index table (raygen.hip) and the one that walks a frame's pixels in order (render_eval.hip): one copy, same bits.
 // Contraction is off inside these functions whatever the including file sets: the reference rounds every product.
@@ -32,6 +32,62 @@ __device__ __forceinline__ PixelRay pixel_ray(int64_t yi, int64_t xi, float fx, 
   cam_to_world(m, (x - cx) / fx, -(y - cy) / fy, -1.f, p.d, p.dir_norm);
   cam_to_world(m, ((x + 1.f) - cx) / fx, -(y - cy) / fy, -1.f, dx, nx);
   cam_to_world(m, (x - cx) / fx, -((y + 1.f) - cy) / fy, -1.f, dy, ny);
+  const float* d0 = p.d;
+  float ax = sqrtf(((d0[0] - dx[0]) * (d0[0] - dx[0]) + (d0[1] - dx[1]) * (d0[1] - dx[1])) + (d0[2] - dx[2]) * (d0[2] - dx[2]));
+  float ay = sqrtf(((d0[0] - dy[0]) * (d0[0] - dy[0]) + (d0[1] - dy[1]) * (d0[1] - dy[1])) + (d0[2] - dy[2]) * (d0[2] - dy[2]));
+  p.o[0] = m[3]; p.o[1] = m[7]; p.o[2] = m[11];
+  p.pixel_area = ax * ay;
+  return p;
+}
+
+// radial_and_tangential_undistort (NS/cameras/camera_utils.py:363-401) of ONE normalised coordinate pair for the OpenCV coefficients
+// k = (k1, k2, k3, k4, p1, p2): Newton on the forward model from the distorted point, ten iterations, no early exit -- the reference runs all
+// ten on every point.  Residual and Jacobian are _compute_residual_and_jacobian's (:298-360) statement by statement, every product rounded
+// (Python's left-to-right association written out).  Both step components are zero when |denominator| <= eps = 1e-3 (torch.where, :395-396).
+// With an all-zero k the residual is exactly zero (d = 1, x * 1 - x), so each step is 0 / -1 and (x, y) come back as they went in.
+__device__ __forceinline__ void undistort_pair(float xd, float yd, const float k[6], float& x_out, float& y_out) {
+#pragma clang fp contract(off)
+  const float k1 = k[0], k2 = k[1], k3 = k[2], k4 = k[3], p1 = k[4], p2 = k[5];
+  float x = xd, y = yd;
+#pragma unroll 1
+  for (int it = 0; it < 10; ++it) {
+    const float r = x * x + y * y;
+    const float d = 1.0f + r * (k1 + r * (k2 + r * (k3 + r * k4)));
+    const float fx = ((d * x + ((2.f * p1) * x) * y) + p2 * (r + (2.f * x) * x)) - xd;
+    const float fy = ((d * y + ((2.f * p2) * x) * y) + p1 * (r + (2.f * y) * y)) - yd;
+    const float d_r = k1 + r * (2.0f * k2 + r * (3.0f * k3 + (r * 4.0f) * k4));
+    const float d_x = (2.0f * x) * d_r;
+    const float d_y = (2.0f * y) * d_r;
+    const float fx_x = ((d + d_x * x) + (2.0f * p1) * y) + (6.0f * p2) * x;
+    const float fx_y = (d_y * x + (2.0f * p1) * x) + (2.0f * p2) * y;
+    const float fy_x = (d_x * y + (2.0f * p2) * y) + (2.0f * p1) * x;
+    const float fy_y = ((d + d_y * y) + (2.0f * p2) * x) + (6.0f * p1) * y;
+    const float den = fy_x * fx_y - fx_x * fy_y;
+    const float xn = fx * fy_y - fy * fx_y;
+    const float yn = fy * fx_x - fx * fy_x;
+    const bool ok = fabsf(den) > 1e-3f;
+    x = x + (ok ? xn / den : 0.f);
+    y = y + (ok ? yn / den : 0.f);
+  }
+  x_out = x; y_out = y;
+}
+
+// pixel_ray through a lens (cameras.py:620-653): the three coordinate pairs -- the pixel, x + 1, y + 1 -- are formed first, and EACH is
+// undistorted on its own, so that the pixel area carries the lens's local Jacobian; from there on it is pixel_ray's code.
+// One deliberate difference in rounding order from the reference: the offsets are formed as pixel_ray forms them, ((x + 1) - cx) / fx and
+// -((y + 1) - cy) / fy, where cameras.py:623-624 writes (x - cx + 1) / fx and -(y - cy + 1) / fy.  For a non-integer cx the two can differ by one
+// float32 ulp of the coordinate.  pixel_ray's form is what makes a zero row equal the pinhole kernel bit for bit; it touches the pixel area only.
+__device__ __forceinline__ PixelRay pixel_ray_lens(int64_t yi, int64_t xi, float fx, float fy, float cx, float cy, const float* m, const float k[6]) {
+#pragma clang fp contract(off)
+  const float y = (float)yi + 0.5f, x = (float)xi + 0.5f;
+  float c[3][2] = {{(x - cx) / fx, -(y - cy) / fy}, {((x + 1.f) - cx) / fx, -(y - cy) / fy}, {(x - cx) / fx, -((y + 1.f) - cy) / fy}};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) undistort_pair(c[i][0], c[i][1], k, c[i][0], c[i][1]);
+  float dx[3], dy[3], nx, ny;
+  PixelRay p;
+  cam_to_world(m, c[0][0], c[0][1], -1.f, p.d, p.dir_norm);
+  cam_to_world(m, c[1][0], c[1][1], -1.f, dx, nx);
+  cam_to_world(m, c[2][0], c[2][1], -1.f, dy, ny);
   const float* d0 = p.d;
   float ax = sqrtf(((d0[0] - dx[0]) * (d0[0] - dx[0]) + (d0[1] - dx[1]) * (d0[1] - dx[1])) + (d0[2] - dx[2]) * (d0[2] - dx[2]));
   float ay = sqrtf(((d0[0] - dy[0]) * (d0[0] - dy[0]) + (d0[1] - dy[1]) * (d0[1] - dy[1])) + (d0[2] - dy[2]) * (d0[2] - dy[2]));

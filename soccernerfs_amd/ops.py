@@ -775,16 +775,24 @@ def fx_to_float(fx: torch.Tensor, out: torch.Tensor, accumulate: bool = False):
     _lib.check(_lib.lib().snerf_fx_to_float(_ptr(fx), _ptr(out), fx.numel(), int(accumulate), _stream()), "fx_to_float")
 
 
-def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_plane: float = 0.0, training: bool = True):
+def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_plane: float = 0.0, training: bool = True, distortion_params=None):
     """RayGenerator.forward (+ AABBBoxCollider when aabb is given).  indices int64 [R,3]; per-camera fx,fy,cx,cy [M],
-    c2w [M,3,4], cam_times [M].  Returns dict of origins, directions, pixel_area, directions_norm, times, (nears, fars)."""
+    c2w [M,3,4], cam_times [M].  Returns dict of origins, directions, pixel_area, directions_norm, times, (nears, fars).
+    distortion_params: None = pinhole rays (snerf_raygen); a float32 tensor [M,6] (one OpenCV row k1 k2 k3 k4 p1 p2 per camera) or [6] (one row
+    for all cameras) = the rays through that lens (snerf_raygen_lens), as the reference's Cameras with distortion_params generates them."""
     if not indices.is_cuda or indices.dtype != torch.int64:
         raise RuntimeError("generate_rays: indices must be an int64 HIP device tensor")
     indices = indices.contiguous()
     R, dev = indices.shape[0], indices.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     out = {"origins": f(R, 3), "directions": f(R, 3), "pixel_area": f(R, 1), "directions_norm": f(R, 1), "times": f(R, 1)}
-    a = _lib.RaygenArgs()
+    lens = distortion_params is not None
+    a = _lib.RaygenLensArgs() if lens else _lib.RaygenArgs()
+    if lens:
+        distortion_params = _f32c(distortion_params, "distortion_params")
+        if tuple(distortion_params.shape) not in ((6,), (c2w.shape[0], 6)):
+            raise RuntimeError(f"generate_rays: distortion_params {tuple(distortion_params.shape)}: expected [6] or [{c2w.shape[0]}, 6]")
+        a.distortion, a.distortion_stride = distortion_params.data_ptr(), 6 if distortion_params.dim() == 2 else 0
     a.indices = indices.data_ptr()
     keep = [_f32c(t, "camera table") for t in (fx, fy, cx, cy, c2w)]
     a.fx, a.fy, a.cx, a.cy, a.c2w = [t.data_ptr() for t in keep]
@@ -800,7 +808,10 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
             a.aabb_min[k], a.aabb_max[k] = ab[0][k], ab[1][k]
         out["nears"], out["fars"] = f(R, 1), f(R, 1)
         a.nears, a.fars = out["nears"].data_ptr(), out["fars"].data_ptr()
-    _lib.check(_lib.lib().snerf_raygen(C.byref(a), _stream()), "raygen")
+    if lens:
+        _lib.check(_lib.lib().snerf_raygen_lens(C.byref(a), _stream()), "raygen_lens")
+    else:
+        _lib.check(_lib.lib().snerf_raygen(C.byref(a), _stream()), "raygen")
     out["camera_indices"] = indices[:, 0:1]
     return out
 

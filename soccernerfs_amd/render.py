@@ -5,7 +5,8 @@ Model.get_outputs_for_camera_ray_bundle (NS/models/base_model.py:159-186) pushes
 --eval-num-rays-per-chunk rays and reshapes rgb / accumulation / depth to [H, W, .].  Here a chunk is one fixed sequence of libsnerf launches
 on the caller's stream, built for inference:
 
-  1. snerf_raygen_frame            rays of the chunk's pixels (no index table) + the AABB collider
+  1. snerf_raygen_frame            rays of the chunk's pixels (no index table) + the AABB collider; snerf_raygen_frame_lens for a camera
+                                   whose distortion row has a non-zero coefficient
   2. snerf_spaced_bins             the first level's bins, no jitter
   3. 2 x (snerf_kplanes_density_fwd + snerf_pdf_resample, u_mode 2)   the proposal levels, eval-mode sampler
   4. snerf_kplanes_field_fwd + snerf_weights_fwd + snerf_render_fwd, or (fused_tail=True / a transmittance cutoff) snerf_kplanes_field_render:
@@ -94,13 +95,15 @@ class KPlanesRenderer:
 
     # ---- cameras ----
     def _host_table(self, cameras: Cameras):
-        """fx, fy, cx, cy, c2w, times of a camera table as host lists (snerf_raygen_frame takes one camera by value): read back once per table."""
+        """fx, fy, cx, cy, c2w, times and distortion rows of a camera table as host lists (snerf_raygen_frame(_lens) takes one camera by value):
+        read back once per table."""
         key = id(cameras)
         hit = self._host_tables.get(key)
         if hit is None or hit[0] is not cameras:
             t = lambda x: x.detach().cpu().tolist()
             hit = (cameras, {"fx": t(cameras.fx), "fy": t(cameras.fy), "cx": t(cameras.cx), "cy": t(cameras.cy),
-                             "c2w": t(cameras.camera_to_worlds.reshape(len(cameras), 12)), "times": None if cameras.times is None else t(cameras.times)})
+                             "c2w": t(cameras.camera_to_worlds.reshape(len(cameras), 12)), "times": None if cameras.times is None else t(cameras.times),
+                             "distortion": t(cameras.distortion_params) if cameras.has_distortion else None})
             self._host_tables = {key: hit}
         return hit[1]
 
@@ -110,12 +113,15 @@ class KPlanesRenderer:
         return anneal_value(max(self.trainer.step - 1, 0), cfg.proposal_weights_anneal_max_num_iters, cfg.proposal_weights_anneal_slope)
 
     # ---- one chunk ----
-    def _chunk(self, ra: _lib.RaygenFrameArgs, p0: int, p1: int, anneal: float, out: Dict[str, torch.Tensor]):
+    def _chunk(self, ra, p0: int, p1: int, anneal: float, out: Dict[str, torch.Tensor]):
         tr, b, rays, lib = self.trainer, self.buf, self._rays, self.lib
         n = p1 - p0
         ra.p0, ra.p1 = p0, p1
         with self._span("raygen_frame"):
-            self._ck(lib.snerf_raygen_frame(C.byref(ra), self._st), "raygen_frame")
+            if isinstance(ra, _lib.RaygenFrameLensArgs):
+                self._ck(lib.snerf_raygen_frame_lens(C.byref(ra), self._st), "raygen_frame_lens")
+            else:
+                self._ck(lib.snerf_raygen_frame(C.byref(ra), self._st), "raygen_frame")
         self.rays, self._fwd_rays = rays, n
         self._spaced_bins(None)
         o, d, t = rays["origins"], rays["directions"], rays["times"]
@@ -184,7 +190,13 @@ class KPlanesRenderer:
             raise ValueError("the cameras carry no times (a camera path has them only if every entry has render_time) and K-Planes is a dynamic "
                              "model: pass default_time")
         H, W = cameras.height, cameras.width
-        ra = _lib.RaygenFrameArgs()
+        row = tab["distortion"][index] if tab["distortion"] is not None else None
+        if row is not None and any(v != 0.0 for v in row):  # the camera's own row: an all-zero row of a lens table is a pinhole camera
+            ra = _lib.RaygenFrameLensArgs()
+            for k in range(6):
+                ra.distortion[k] = row[k]
+        else:
+            ra = _lib.RaygenFrameArgs()
         ra.fx, ra.fy, ra.cx, ra.cy = tab["fx"][index], tab["fy"][index], tab["cx"][index], tab["cy"][index]
         ra.time = tab["times"][index] if tab["times"] is not None else float(default_time)
         for k in range(12):

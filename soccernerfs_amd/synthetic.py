@@ -261,13 +261,19 @@ def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor) -> torch
 
 def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, device, chunk_rows: int = 135, variant: str = "default") -> Dict[str, torch.Tensor]:
     """uint8 images [M,H,W,3] on `device` for every (camera in cam_ids) x (time), plus per-image camera tables
-    (one 'camera' per image, as nerfstudio's Cameras object holds them: c2w/intrinsics repeated per frame + times)."""
+    (one 'camera' per image, as nerfstudio's Cameras object holds them: c2w/intrinsics repeated per frame + times).
+    cams may carry "distortion": OpenCV rows k1 k2 k3 k4 p1 p2, [n_cams,6] or [6] for all cameras.  The dataset is then shot through that lens
+    (ops.generate_rays(distortion_params=...)) and the returned table carries "distortion" [M,6]; without the entry nothing changes."""
     from . import ops
 
     H, W = cams["height"], cams["width"]
     M = len(cam_ids) * len(times)
     imgs = torch.empty(M, H, W, 3, dtype=torch.uint8, device=device)
     tab = {k: [] for k in ("c2w", "fx", "fy", "cx", "cy", "times", "cam_id")}
+    lens = cams.get("distortion")
+    if lens is not None:
+        lens = torch.as_tensor(lens, dtype=torch.float32).reshape(-1, 6)
+        tab["distortion"] = []
     m = 0
     for c in cam_ids:
         for t in times.tolist():
@@ -275,6 +281,8 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
                 tab[k].append(cams[k][c])
             tab["times"].append(t)
             tab["cam_id"].append(c)
+            if lens is not None:
+                tab["distortion"].append(lens[c if lens.shape[0] > 1 else 0])
             m += 1
     table = {k: torch.stack(v).to(device).contiguous() for k, v in tab.items() if k not in ("times", "cam_id")}
     table["times"] = torch.tensor(tab["times"], dtype=torch.float32, device=device)
@@ -285,7 +293,8 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             rows = torch.arange(r0, min(r0 + chunk_rows, H), device=device)
             yy, xx = torch.meshgrid(rows, xs, indexing="ij")
             idx = torch.stack([torch.full_like(yy, m), yy, xx], -1).reshape(-1, 3)
-            rays = ops.generate_rays(idx, table["fx"], table["fy"], table["cx"], table["cy"], table["c2w"], table["times"])
+            rays = ops.generate_rays(idx, table["fx"], table["fy"], table["cx"], table["cy"], table["c2w"], table["times"],
+                                     distortion_params=table.get("distortion"))
             col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant)
             imgs[m, r0:r0 + rows.numel()] = (col.view(rows.numel(), W, 3) * 255.0 + 0.5).to(torch.uint8)
     return {"images": imgs, **table, "width": W, "height": H}

@@ -44,7 +44,7 @@ def eval_set(trainer, data, image_ids, anneal, with_ssim=True):
         out = torch.empty(H * W, 3, device=imgs.device)
         for i in range(0, H * W, R):
             rays = ops.generate_rays(idx[i:i + R].contiguous(), data["fx"], data["fy"], data["cx"], data["cy"], data["c2w"], data["times"],
-                                     aabb=trainer.aabb, near_plane=trainer.cfg.near_plane, training=False)
+                                     aabb=trainer.aabb, near_plane=trainer.cfg.near_plane, training=False, distortion_params=data.get("ray_distortion"))
             out[i:i + R] = trainer.forward(rays, None, anneal, training=False)
         gt = imgs[m].reshape(-1, 3).float() / 255.0
         mse = torch.mean((out - gt) ** 2)
@@ -124,7 +124,7 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
             idx = ops.sort_rays_by_time(idx, time_key, n_time_keys)
         target = train["images"][idx[:, 0], idx[:, 1], idx[:, 2]].float() / 255.0
         rays = ops.generate_rays(idx, train["fx"], train["fy"], train["cx"], train["cy"], train["c2w"], train["times"], aabb=trainer.aabb,
-                                 near_plane=cfg.near_plane, training=True)
+                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"))
         trainer.train_step(rays, target)
         if args.standin and step % 100 == 99:
             print(f"[standin seed {seed}] step {step + 1} {time.time() - t1:.1f}s into this thousand", flush=True)
@@ -184,13 +184,33 @@ def main():
     ap.add_argument("--oracle-init", action="store_true", help="HIP trainer from the stand-in's initial parameters of the same seed")
     ap.add_argument("--scene", default="default", choices=["default", "textured"], help="synthetic.shade variant (textured: grass grain, board, crowd, ten players)")
     ap.add_argument("--no-overlap", action="store_true", help="single-stream step (A/B against stream-ordering effects)")
-    args = ap.parse_args()
+    # a value such as -0.25,0.08,... starts with '-' and is no plain number, so argparse would read it as an option: hand it over as --lens=VALUE
+    argv = sys.argv[1:]
+    for i in range(len(argv) - 1):
+        if argv[i] == "--lens":
+            argv[i:i + 2] = ["--lens=" + argv[i + 1]]
+            break
+    ap.add_argument("--lens", default="", help="k1,k2,k3,k4,p1,p2 (`--lens -0.25,0.08,-0.01,0,0.001,0.0005` or `--lens=...`): every training and held-out camera shoots the scene through this OpenCV lens, and "
+                    "training and evaluation generate their rays through it (snerf_raygen_lens)")
+    ap.add_argument("--ignore-lens", action="store_true", help="with --lens: the dataset is still shot through the lens, but training and evaluation use "
+                    "pinhole rays -- what this package did before it generated rays through the distortion")
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     cams = synthetic.make_cameras(20, 960, 540)
+    novel_cams = synthetic.make_novel_cameras(3, 960, 540)
+    if args.lens:
+        row = [float(v) for v in args.lens.split(",")]
+        if len(row) != 6:
+            ap.error("--lens takes six numbers: k1,k2,k3,k4,p1,p2")
+        cams["distortion"], novel_cams["distortion"] = torch.tensor(row), torch.tensor(row)
+    elif args.ignore_lens:
+        ap.error("--ignore-lens needs --lens")
     times = synthetic.frame_times(100, 3)
     train = synthetic.render_dataset(cams, times, list(range(19)), dev, chunk_rows=540, variant=args.scene)
     held = synthetic.render_dataset(cams, times, [19], dev, chunk_rows=540, variant=args.scene)
-    novel = synthetic.render_dataset(synthetic.make_novel_cameras(3, 960, 540), times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene)
+    novel = synthetic.render_dataset(novel_cams, times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene)
+    for data in (train, held, novel):  # the rows the rays of training and evaluation go through: the dataset's own, or none with --ignore-lens
+        data["ray_distortion"] = None if args.ignore_lens else data.get("distortion")
     t0 = time.time()
     ist = compute_ist(train["images"], train["cam_id"], train["times"], ist_range=1.0)  # method_configs.py:503
     torch.cuda.synchronize()
@@ -199,7 +219,8 @@ def main():
                           for f in torch.linspace(0, len(times) - 1, args.eval_frames).long().tolist()])
     sets = {"camera_20": (held, pick(held)), "novel": (novel, pick(novel)),
             "train": (train, torch.linspace(0, train["images"].shape[0] - 1, 4).long().tolist())}
-    log = {"config": "k-planes preset, synthetic Broadcast-style (19 train cams x 33 frames 960x540)", "steps": args.steps, "scene": args.scene, "eval_frames": args.eval_frames or "all",
+    log = {"config": "k-planes preset, synthetic Broadcast-style (19 train cams x 33 frames 960x540)", "steps": args.steps, "scene": args.scene,
+           "lens": args.lens or None, "ignore_lens": args.ignore_lens, "eval_frames": args.eval_frames or "all",
            "trainer": ("oracle/torch_standin.StandinTrainer: the reference's algorithm in stock PyTorch-ROCm, fp32"
                        + (", planes stored channel-last and gathered as rows (index_select) instead of F.grid_sample" if args.standin_layout == "hwc" else ", F.grid_sample per plane"))
            if args.standin else "soccernerfs_amd KPlanesTrainer (HIP)",

@@ -4,8 +4,7 @@
 // for the generic MLP kernels (the exact-fp32 path, the unfused forward, deterministic mode), and the slice of their gX back into gh.  The 16-bit
 // training path does not build X at all: the fused field forward (field_fused.hip) and the colour backward (mlp_rows.hip, snerf_kplanes_color_bwd_vd)
 // form it on chip from the same per-ray directions.  The SH columns are sh4_common.hpp's, bit-identical to soccernerfs_amd/sh.py.
-#include "common.hpp"
-#include "mlp_lp_common.hpp"
+#include "mlp_args.hpp"
 #include "sh4_common.hpp"
 
 namespace snerf {
@@ -38,9 +37,6 @@ __global__ __launch_bounds__(256) void color_input_bwd_kernel(const float* __res
   gh[n * 16 + c] = gX[n * ldgx + 16 + c];
 }
 
-bool mlp_rows_vd_supported(const snerf_mlp_desc* d);
-int mlp_rows_vd_dispatch(const snerf_mlp_desc* d, const MlpArgs& a, hipStream_t st);
-
 static int color_bwd_vd_impl(const snerf_mlp_desc* d, const float* W, const float* dirs, int32_t S, const float* h, int64_t N, const float* gY,
                              int32_t ldgy, float* gh, float* gW, float* ws, snerf_stream_t stream) {
   SNERF_REQUIRE(d && mlp_rows_vd_supported(d), "color_bwd_vd: the kernel is built for 31 -> 64 -> 64 -> 3 (ReLU, Sigmoid) with bf16 / fp16 operands");
@@ -55,8 +51,7 @@ static int color_bwd_vd_impl(const snerf_mlp_desc* d, const float* W, const floa
   a.X = h; a.ldx = 16; a.N = N; a.W = W; a.gY = gY; a.ldgy = ldgy; a.gX = gh; a.ldgx = 16;
   a.dirs = dirs; a.S = S;
   if (ws) {
-    a.ws = ws; a.ws_rep = GW_REPLICAS;
-    a.ws_stride = ((int64_t)31 * 64 + 64 * 64 + 64 * 3 + 63) / 64 * 64;  // = mlp.hip's gw_ws_stride: snerf_mlp_gw_reduce folds it
+    a.ws = ws; a.ws_rep = GW_REPLICAS; a.ws_stride = gw_ws_stride(d);  // snerf_mlp_gw_reduce folds it
   } else {
     a.gW = gW;
   }

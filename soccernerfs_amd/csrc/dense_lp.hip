@@ -206,25 +206,12 @@ __global__ __launch_bounds__((waves<KP, MP>() * 64)) void dense_lp_bwd_kernel(Ml
 template <typename T, int KP, int MP>
 static int launch(const MlpArgs& a, bool bwd, hipStream_t st) {
   const int64_t n_tiles = (a.N + TS - 1) / TS;
-  const size_t bytes = bwd ? BwdPlan<T, KP, MP>::BYTES : FwdPlan<T, KP, MP>::BYTES;
-  static_assert(BwdPlan<T, KP, MP>::BYTES <= LDS_LIMIT_B, "dense_lp backward does not fit LDS");
-  int per_cu = (int)(LDS_LIMIT_B / bytes);
-  const int by_waves = 16 / waves<KP, MP>();  // at most 4 waves per SIMD worth of workgroups; registers decide the rest
-  per_cu = per_cu < 1 ? 1 : (per_cu > by_waves ? by_waves : per_cu);
-  if (per_cu > 2) per_cu = 2;
-  int64_t grid = 256 * per_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  if (bwd) {
-    auto k = dense_lp_bwd_kernel<T, KP, MP>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves<KP, MP>() * 64), bytes, st, a, n_tiles);
-  } else {
-    auto k = dense_lp_fwd_kernel<T, KP, MP>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves<KP, MP>() * 64), bytes, st, a, n_tiles);
-  }
-  SNERF_LAUNCH_CHECK(bwd ? "dense_bwd_lp" : "dense_fwd_lp");
-  return 0;
+  static_assert(BwdPlan<T, KP, MP>::BYTES <= LDS_LIMIT, "dense_lp backward does not fit LDS");
+  constexpr int NT = waves<KP, MP>() * 64;
+  const int by_waves = 16 / waves<KP, MP>();  // at most 4 waves per SIMD worth of workgroups; registers decide the rest: two
+  const int cap = by_waves < 2 ? by_waves : 2;
+  if (bwd) return launch_persistent<dense_lp_bwd_kernel<T, KP, MP>>(a, n_tiles, BwdPlan<T, KP, MP>::BYTES, cap, NT, st, "dense_bwd_lp");
+  return launch_persistent<dense_lp_fwd_kernel<T, KP, MP>>(a, n_tiles, FwdPlan<T, KP, MP>::BYTES, cap, NT, st, "dense_fwd_lp");
 }
 
 static int dispatch(int K, int M, const MlpArgs& a, bool bwd, hipStream_t st) {

@@ -55,12 +55,12 @@ template <typename T, int NS, int KEEP, bool VD>
 static int launch_field_fwd_k(const FieldArgs& a, hipStream_t st) {
   using P = PlanFF<NS>;
   const int64_t n_tiles = (a.N + FF_TS - 1) / FF_TS;
-  int per_cu = (int)(LDS_LIMIT_B / P::BYTES);
+  int per_cu = (int)(LDS_LIMIT / P::BYTES);
   per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // 125 VGPRs: two 8-wave workgroups per CU
   int64_t grid = 256 * per_cu;
   if (grid > n_tiles) grid = n_tiles;
   auto k = field_fwd_kernel<T, NS, KEEP, VD>;
-  SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+  SNERF_ALLOW_LDS(k, LDS_LIMIT);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, n_tiles);
   SNERF_LAUNCH_CHECK("kplanes_field_fwd");
   return 0;

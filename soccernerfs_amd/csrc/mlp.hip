@@ -16,43 +16,11 @@
 //     keeps the weight-gradient accumulators in registers across the whole persistent loop and flushes them once per workgroup
 //     with 64-B-contiguous atomics.  TS (64/32/16) is chosen per shape so that weights + tiles fit and, for 4-wave workgroups,
 //     two of them share a CU.
-#include "common.hpp"
+#include "mlp_args.hpp"
 
 namespace snerf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int OUTP = 16;  // padded output width (all nets here have <= 16 outputs)
-constexpr int LDS_LIMIT = 160 * 1024;
-
-struct MlpArgs {
-  const float* X; int64_t N; int ldx; int d0;
-  const float* W; int woff[4];
-  int dout;
-  float* Y; int ldy;
-  int hidden_act, out_act;
-  int aux_col; float* aux_out;
-  const float* gY; int ldgy;
-  const float* gaux;
-  float* gX; int ldgx;
-  float* gW;
-  long long* gWfx;  // deterministic mode: weight gradients accumulate here as fixed point instead (common.hpp)
-  int x16;          // X holds the 16-bit operand type (what snerf_kplanes_field_fwd wrote), not fp32: 16-bit kernels only
-  // quotient epilogue of the backward (snerf_mlp_bwd_x16_quotient; 16-bit kernels, one hidden layer of 128): instead of gX the kernel writes
-  // G = gX .* X (X = the 16-bit tile it holds in LDS) and lists the elements whose X vanished while gX did not (common.hpp: fix_append)
-  float* G; int ldg;
-  int32_t* fix_list; int fix_capacity;
-  int32_t* fix_count; int32_t* fix_count_next;
-  int variant;      // backward only: 0 = the default kernel for the shape, 1 = the workgroup-tile kernels of mlp_lp.hip (snerf_mlp_bwd_tile)
-  float* ws; int ws_rep; int64_t ws_stride;  // weight-gradient workspace (mlp_lp_common.hpp; honoured by the 16-bit kernels only)
-  // dense layers wider than one 128 x 128 block (snerf_dense_fwd / _bwd tile them): row stride of W in global memory (0 = dout), and
-  // "add to what is there" for the forward's output (later K blocks of a linear layer) / the backward's input gradient (later column blocks)
-  int ldw_g, acc_y, acc_gx;
-};
-
-__device__ __forceinline__ void gw_add(const MlpArgs& a, int64_t idx, float v) {
-  if (a.gWfx) fx_atomic_add(a.gWfx + idx, v); else atomicAdd(a.gW + idx, v);
-}
 
 __host__ __device__ constexpr int ld_of(int width) { return ((width + 31) / 32) * 32 + 2; }  // = 2 mod 32
 __host__ __device__ constexpr int ldw_of(int n) { return n == OUTP ? 18 : ld_of(n); }
@@ -573,7 +541,7 @@ __global__ __launch_bounds__(waves_of<H>() * 64) void mlp_bwd_kernel(MlpArgs a, 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = it * 16 + r0 + r, col = nt * 16 + cl;
-          if (row < a.d0) gw_add(a, a.woff[0] + (int64_t)row * H + col, dW0[j][r]);
+          if (row < a.d0) gw_add<false>(a, a.woff[0] + (int64_t)row * H + col, dW0[j][r]);
         }
       }
     }
@@ -584,7 +552,7 @@ __global__ __launch_bounds__(waves_of<H>() * 64) void mlp_bwd_kernel(MlpArgs a, 
         if (t < HT * HT) {
           const int it = t / HT, nt = t % HT;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) gw_add(a, a.woff[1] + (int64_t)(it * 16 + r0 + r) * H + nt * 16 + cl, dWh[j][r]);
+          for (int r = 0; r < 4; ++r) gw_add<false>(a, a.woff[1] + (int64_t)(it * 16 + r0 + r) * H + nt * 16 + cl, dWh[j][r]);
         }
       }
     }
@@ -594,7 +562,7 @@ __global__ __launch_bounds__(waves_of<H>() * 64) void mlp_bwd_kernel(MlpArgs a, 
       if (it < HT) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (cl < a.dout) gw_add(a, a.woff[NH] + (int64_t)(it * 16 + r0 + r) * a.dout + cl, dWo[j][r]);
+          if (cl < a.dout) gw_add<false>(a, a.woff[NH] + (int64_t)(it * 16 + r0 + r) * a.dout + cl, dWo[j][r]);
       }
     }
   }
@@ -731,7 +699,7 @@ __global__ __launch_bounds__(dense_waves<MP>() * 64) void dense_bwd_kernel(MlpAr
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = it * 16 + r0 + r, col = nt * 16 + cl;
-          if (row < a.d0 && col < a.dout) gw_add(a, (int64_t)row * (a.ldw_g > 0 ? a.ldw_g : a.dout) + col, dW[j][r]);
+          if (row < a.d0 && col < a.dout) gw_add<false>(a, (int64_t)row * (a.ldw_g > 0 ? a.ldw_g : a.dout) + col, dW[j][r]);
         }
       }
     }
@@ -742,28 +710,9 @@ template <int KP, int MP>
 static int launch_dense(const MlpArgs& a, bool bwd, hipStream_t st) {
   constexpr int TS = 64;
   const int64_t n_tiles = (a.N + TS - 1) / TS;
-  if (bwd) {
-    using P = DensePlan<KP, MP, TS, true>;
-    static_assert(P::BYTES <= LDS_LIMIT, "dense backward tile does not fit LDS");
-    int per_cu = (int)(LDS_LIMIT / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = dense_bwd_kernel<KP, MP, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(dense_waves<MP>() * 64), P::BYTES, st, a, n_tiles);
-  } else {
-    using P = DensePlan<KP, MP, TS, false>;
-    int per_cu = (int)(LDS_LIMIT / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = dense_fwd_kernel<KP, MP, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(dense_waves<MP>() * 64), P::BYTES, st, a, n_tiles);
-  }
-  SNERF_LAUNCH_CHECK(bwd ? "dense_bwd" : "dense_fwd");
-  return 0;
+  static_assert(DensePlan<KP, MP, TS, true>::BYTES <= LDS_LIMIT, "dense backward tile does not fit LDS");
+  if (bwd) return launch_persistent<dense_bwd_kernel<KP, MP, TS>>(a, n_tiles, DensePlan<KP, MP, TS, true>::BYTES, 2, dense_waves<MP>() * 64, st, "dense_bwd");
+  return launch_persistent<dense_fwd_kernel<KP, MP, TS>>(a, n_tiles, DensePlan<KP, MP, TS, false>::BYTES, 2, dense_waves<MP>() * 64, st, "dense_fwd");
 }
 
 static int dispatch_dense(int K, int M, const MlpArgs& a, bool bwd, hipStream_t st) {
@@ -785,41 +734,17 @@ static int launch(const MlpArgs& a, bool bwd, hipStream_t st) {
     constexpr int TS = pick_ts<D0P, H, NH, true>();
     using P = Plan<D0P, H, NH, TS, true>;
     static_assert(P::BYTES <= LDS_LIMIT, "backward tile does not fit LDS");
-    const int64_t n_tiles = (a.N + TS - 1) / TS;
-    int per_cu = (int)(LDS_LIMIT / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = mlp_bwd_kernel<D0P, H, NH, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_of<H>() * 64), P::BYTES, st, a, n_tiles);
+    return launch_persistent<mlp_bwd_kernel<D0P, H, NH, TS>>(a, (a.N + TS - 1) / TS, P::BYTES, 4, waves_of<H>() * 64, st, "mlp_bwd");
   } else if (NH == 1 && H / 16 == waves_of<H>()) {
     constexpr int TS = H >= 128 ? 16 : 64;
-    using P = PlanWreg<D0P, H, TS>;
-    const int64_t n_tiles = (a.N + TS - 1) / TS;
-    int per_cu = (int)(LDS_LIMIT / P::BYTES);
     const int by_regs = H >= 128 ? 2 : 4;  // 8-wave workgroups holding D0P/4 weight registers per lane: two per CU
-    per_cu = per_cu < 1 ? 1 : (per_cu > by_regs ? by_regs : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = mlp_fwd_wreg_kernel<D0P, H, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(H / 16 * 64), P::BYTES, st, a, n_tiles);
+    return launch_persistent<mlp_fwd_wreg_kernel<D0P, H, TS>>(a, (a.N + TS - 1) / TS, PlanWreg<D0P, H, TS>::BYTES, by_regs, H / 16 * 64, st, "mlp_fwd");
   } else {
     constexpr int TS = pick_ts<D0P, H, NH, false>();
     using P = Plan<D0P, H, NH, TS, false>;
     static_assert(P::BYTES <= LDS_LIMIT, "forward tile does not fit LDS");
-    const int64_t n_tiles = (a.N + TS - 1) / TS;
-    int per_cu = (int)(LDS_LIMIT / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = mlp_fwd_kernel<D0P, H, NH, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_of<H>() * 64), P::BYTES, st, a, n_tiles);
+    return launch_persistent<mlp_fwd_kernel<D0P, H, NH, TS>>(a, (a.N + TS - 1) / TS, P::BYTES, 4, waves_of<H>() * 64, st, "mlp_fwd");
   }
-  SNERF_LAUNCH_CHECK(bwd ? "mlp_bwd" : "mlp_fwd");
-  return 0;
 }
 
 // (padded input width, hidden width, hidden layers) the fused kernels are instantiated for
@@ -841,12 +766,8 @@ static int launch(const MlpArgs& a, bool bwd, hipStream_t st) {
   X(48, 64, 2)                                                                \
   X(64, 64, 2)   /* nerfplayer mlp_head 63->64->64->3 */
 
-// bf16-operand kernels (mlp_lp.hip)
-bool mlp_bf16_supported(const snerf_mlp_desc* d);
-int mlp_bf16_dispatch(const snerf_mlp_desc* d, const void* args, bool bwd, hipStream_t st);
-
 static int dispatch(const snerf_mlp_desc* d, const MlpArgs& a, bool bwd, hipStream_t st) {
-  if (d->operands != 0) return mlp_bf16_dispatch(d, &a, bwd, st);
+  if (d->operands != 0) return mlp_bf16_dispatch(d, a, bwd, st);  // 16-bit operands: mlp_lp.hip
   const int d0p = (d->d_in + 15) / 16 * 16;
 #define CASE(D0P, H, NH) \
   if (d0p == D0P && d->hidden == H && d->n_hidden == NH) return launch<D0P, H, NH>(a, bwd, st);
@@ -887,15 +808,7 @@ extern "C" int snerf_mlp_supported(const snerf_mlp_desc* d) {
   return 0;
 }
 
-// weight-gradient workspace of snerf_mlp_bwd_ws: GW_REPLICAS_H replicas of the flat gradient, each padded to 64 floats
-constexpr int GW_REPLICAS_H = 16;  // = mlp_lp_common.hpp's GW_REPLICAS
-static int64_t gw_ws_stride(const snerf_mlp_desc* d) {
-  int64_t n = 0, prev = d->d_in;
-  for (int l = 0; l < d->n_hidden; ++l) { n += prev * d->hidden; prev = d->hidden; }
-  n += prev * d->d_out;
-  return (n + 63) / 64 * 64;
-}
-
+// folds the GW_REPLICAS replicas of a snerf_mlp_bwd_ws workspace (mlp_args.hpp: gw_ws_stride floats apart) into gW and clears them
 __global__ __launch_bounds__(256) void gw_reduce_kernel(float* __restrict__ ws, int64_t stride, int reps, float* __restrict__ gW, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -944,7 +857,7 @@ static int mlp_bwd_impl(const snerf_mlp_desc* d, const float* W, const float* X,
   a.gWfx = gWfx;
   a.x16 = x16;
   a.variant = variant;
-  if (ws && d->operands != 0) { a.ws = ws; a.ws_rep = GW_REPLICAS_H; a.ws_stride = gw_ws_stride(d); }
+  if (ws && d->operands != 0) { a.ws = ws; a.ws_rep = GW_REPLICAS; a.ws_stride = gw_ws_stride(d); }
   else if (ws) { a.gW = ws; }  // exact-fp32 kernels: no replica routing -- everything lands in replica 0, which the reduce folds in like the others
   SNERF_REQUIRE(!x16 || d->operands == 1 || d->operands == 2, "mlp_bwd_x16: a 16-bit input needs 16-bit operands (desc.operands = 1 / 2), got %d", d->operands);
   return dispatch(d, a, true, (hipStream_t)stream);
@@ -957,7 +870,7 @@ extern "C" int snerf_mlp_bwd(const snerf_mlp_desc* d, const float* W, const floa
 
 extern "C" int64_t snerf_mlp_gw_workspace_floats(const snerf_mlp_desc* d) {
   if (!d || d->d_in < 1 || d->n_hidden < 1 || d->n_hidden > 2) return -1;
-  return GW_REPLICAS_H * gw_ws_stride(d);
+  return GW_REPLICAS * gw_ws_stride(d);
 }
 
 extern "C" int snerf_mlp_bwd_ws(const snerf_mlp_desc* d, const float* W, const float* X, int32_t ldx, int64_t N, const float* gY, int32_t ldgy,
@@ -970,7 +883,7 @@ extern "C" int snerf_mlp_gw_reduce(const snerf_mlp_desc* d, float* workspace, fl
   SNERF_REQUIRE(d && workspace && gW, "mlp_gw_reduce: null argument");
   const int64_t n = snerf_mlp_param_count(d);
   SNERF_REQUIRE(n > 0, "mlp_gw_reduce: bad descriptor");
-  hipLaunchKernelGGL(gw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, workspace, gw_ws_stride(d), GW_REPLICAS_H, gW, n);
+  hipLaunchKernelGGL(gw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, workspace, gw_ws_stride(d), GW_REPLICAS, gW, n);
   SNERF_LAUNCH_CHECK("mlp_gw_reduce");
   return 0;
 }
@@ -1021,7 +934,7 @@ static int mlp_bwd_x16_quotient_impl(const snerf_mlp_desc* d, const float* W, co
   a.X = reinterpret_cast<const float*>(X16); a.N = N; a.ldx = ldx; a.W = W; a.gY = gY; a.ldgy = ldgy; a.aux_col = aux_col; a.gaux = gaux; a.gW = gW;
   a.x16 = 1;
   a.G = G; a.ldg = ldg; a.fix_list = fix_list; a.fix_capacity = fix_capacity; a.fix_count = fix_count; a.fix_count_next = fix_count_next;
-  if (ws) { a.ws = ws; a.ws_rep = GW_REPLICAS_H; a.ws_stride = gw_ws_stride(d); }
+  if (ws) { a.ws = ws; a.ws_rep = GW_REPLICAS; a.ws_stride = gw_ws_stride(d); }
   return dispatch(d, a, true, st);
 }
 

@@ -93,6 +93,11 @@ struct XTile16 {
 template <int H>
 constexpr int waves_b() { return H >= 128 ? 8 : 4; }
 
+__device__ __forceinline__ f32x4 relu4(f32x4 v, bool relu) {
+  if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+  return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
@@ -136,11 +141,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_fwd_kernel(MlpArgs a
         f32x4 acc[MT] = {};
         mma_rr<MT, K0>(smem + P::XS, P::LK0, smem + P::W0T, P::LK0, nt, acc, lane);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          f32x4 v = acc[m];
-          if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-          store_rt<T>(smem + P::A1, P::LKH, nullptr, 0, m, nt, v, lane);
-        }
+        for (int m = 0; m < MT; ++m) store_rt<T>(smem + P::A1, P::LKH, nullptr, 0, m, nt, relu4(acc[m], relu), lane);
       }
     }
     __syncthreads();
@@ -152,11 +153,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_fwd_kernel(MlpArgs a
           f32x4 acc[MT] = {};
           mma_rr<MT, H>(smem + P::A1, P::LKH, smem + P::W1T, P::LKH, nt, acc, lane);
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            f32x4 v = acc[m];
-            if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-            store_rt<T>(smem + P::A2, P::LKH, nullptr, 0, m, nt, v, lane);
-          }
+          for (int m = 0; m < MT; ++m) store_rt<T>(smem + P::A2, P::LKH, nullptr, 0, m, nt, relu4(acc[m], relu), lane);
         }
       }
       __syncthreads();
@@ -253,6 +250,25 @@ struct PlanB {
   static constexpr size_t BYTES = (size_t)TOTAL * 2;
 };
 
+// The two workgroup-tile backward kernels below (mlp_lp_bwd_kernel: two LDS images per tile; mlp_lp_bwd_tr_kernel: transposed reads) share relu4 and
+// this product and nothing else of their bodies, on purpose.  Their W0 prologue, gY / gaux prefetch, layer-0 forward, output gradient, row-block gX
+// epilogue and weight-gradient flush read alike, and each was tried as a shared __forceinline__ function (round 13): every one of them moved
+// VGPR counts in 8 to 38 of the 42 instantiations, by up to + 20 and for some across an occupancy step, though the inlined source is the same --
+// profiles/r13_mlp_INDEX.md has the table.  Only the two pieces that left every instantiation's registers, scratch and occupancy alone stayed.
+// dWO += A_last^T gzo: both unit-major ([unit][sample], [output][sample]), the contraction runs over the tile's samples
+template <typename T, int TS, int H, int NW, int NBO>
+__device__ __forceinline__ void accum_dwo(const T* Alt, const T* gzot, int ldt, f32x4 (&dWo)[NBO], int wave, int lane) {
+#pragma unroll
+  for (int j = 0; j < NBO; ++j) {
+    const int it = wave + NW * j;
+    if (it < H / 16) {
+      f32x4 acc[1] = {dWo[j]};
+      mma_rr<1, TS>(Alt + it * 16 * ldt, ldt, gzot, ldt, 0, acc, lane);
+      dWo[j] = acc[0];
+    }
+  }
+}
+
 // (Round 2 also formed the quotient scatter's G = gX .* feat in this kernel's gX epilogue: that instantiation needed 256 VGPRs + spills and the
 // step got slower -- profiles/r02_kernels.md section 10 -- so the separate quotient_prepare pass stayed and the variant was removed.  A lesson
 // kept: an optional epilogue must be a template parameter; as a run-time `if` EVERY instantiation paid its registers.)
@@ -342,13 +358,9 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_kernel(MlpArgs a
         } else {
           mma_rr<MT, K0>(Xs, P::LK0, smem + P::W0T, P::LK0, nt, acc, lane);
         }
+        // one hidden layer: only the unit-major image; the output layer and the relu mask read it back (transposed / 8 bytes per block)
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          f32x4 v = acc[m];
-          if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-          // one hidden layer: only the unit-major image; the output layer and the relu mask read it back (transposed / 8 bytes per block)
-          store_rt(NH == 1 ? (T*)nullptr : A1, P::LKH, A1t, P::LKT, m, nt, v, lane);
-        }
+        for (int m = 0; m < MT; ++m) store_rt(NH == 1 ? (T*)nullptr : A1, P::LKH, A1t, P::LKT, m, nt, relu4(acc[m], relu), lane);
       }
     }
     __syncthreads();
@@ -360,11 +372,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_kernel(MlpArgs a
           f32x4 acc[MT] = {};
           mma_rr<MT, H>(A1, P::LKH, smem + P::W1T, P::LKH, nt, acc, lane);
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            f32x4 v = acc[m];
-            if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-            store_rt(Al, P::LKH, Alt, P::LKT, m, nt, v, lane);
-          }
+          for (int m = 0; m < MT; ++m) store_rt(Al, P::LKH, Alt, P::LKT, m, nt, relu4(acc[m], relu), lane);
         }
       }
       __syncthreads();
@@ -399,16 +407,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_kernel(MlpArgs a
       }
     }
     __syncthreads();
-    // ---- dWO += A_last^T gzo (contraction over the tile's samples) ----
-#pragma unroll
-    for (int j = 0; j < NBO; ++j) {
-      const int it = wave + NW * j;
-      if (it < HT) {
-        f32x4 acc[1] = {dWo[j]};
-        mma_rr<1, TS>(Alt + it * 16 * P::LKT, P::LKT, gzot, P::LKT, 0, acc, lane);
-        dWo[j] = acc[0];
-      }
-    }
+    accum_dwo<T, TS, H, NW>(Alt, gzot, P::LKT, dWo, wave, lane);
     __syncthreads();  // Alt is overwritten by gzt below
     // ---- gz = (gzo WO^T) .* relu'(A_last): row-major and transposed ----
 #pragma unroll
@@ -695,11 +694,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_tr_kernel(MlpArg
           mma_rr<MT, K0>(Xs, P::LK0, smem + P::W0T, P::LK0, nt, acc, lane);
         }
 #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          f32x4 v = acc[m];
-          if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-          store_rt<T>(nullptr, 0, A1t, P::LKT, m, nt, v, lane);
-        }
+        for (int m = 0; m < MT; ++m) store_rt<T>(nullptr, 0, A1t, P::LKT, m, nt, relu4(acc[m], relu), lane);
       }
     }
     __syncthreads();
@@ -711,11 +706,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_tr_kernel(MlpArg
           f32x4 acc[MT] = {};
           mma_tr<MT, H, T>(A1t, P::LKT, 0, smem + P::W1T, P::LKH, nt, acc, lane);
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            f32x4 v = acc[m];
-            if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-            store_rt<T>(nullptr, 0, Alt, P::LKT, m, nt, v, lane);
-          }
+          for (int m = 0; m < MT; ++m) store_rt<T>(nullptr, 0, Alt, P::LKT, m, nt, relu4(acc[m], relu), lane);
         }
       }
       __syncthreads();
@@ -749,16 +740,7 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_tr_kernel(MlpArg
       }
     }
     __syncthreads();
-    // ---- dWO += A_last^T gzo (contraction over the tile's samples) ----
-#pragma unroll
-    for (int j = 0; j < NBO; ++j) {
-      const int it = wave + NW * j;
-      if (it < HT) {
-        f32x4 acc[1] = {dWo[j]};
-        mma_rr<1, TS>(Alt + it * 16 * P::LKT, P::LKT, gzot, P::LKT, 0, acc, lane);
-        dWo[j] = acc[0];
-      }
-    }
+    accum_dwo<T, TS, H, NW>(Alt, gzot, P::LKT, dWo, wave, lane);
     __syncthreads();  // Alt is overwritten below
     // ---- gradient of Z_last = (gzo WO^T) .* relu'(A_last), over A_last; gzo read transposed ----
 #pragma unroll
@@ -890,93 +872,53 @@ __global__ __launch_bounds__(waves_b<H>() * 64) void mlp_lp_bwd_tr_kernel(MlpArg
   }
 }
 
+// every launch below: persistent workgroups over the tiles (mlp_args.hpp: launch_persistent)
 template <typename T, int K0, int H, int NH, bool X16>
 static int launch_b_tr(const MlpArgs& a, hipStream_t st) {
-  constexpr int TS = 64;
+  constexpr int TS = 64, NW = waves_b<H>();
   using P = PlanT<K0, H, NH, TS>;
-  static_assert(P::BYTES <= LDS_LIMIT_B, "transposed-read backward tile does not fit LDS");
-  const int64_t n_tiles = (a.N + TS - 1) / TS;
-  int per_cu = (int)(LDS_LIMIT_B / P::BYTES);
-  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-  if (waves_b<H>() * per_cu > 8) per_cu = 8 / waves_b<H>();  // the kernels hold 130-250 VGPRs: two waves per SIMD
-  int64_t grid = 256 * per_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  auto k = mlp_lp_bwd_tr_kernel<T, K0, H, NH, TS, X16>;
-  SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_b<H>() * 64), P::BYTES, st, a, n_tiles);
-  SNERF_LAUNCH_CHECK("mlp_bwd (16-bit operands, transposed reads)");
-  return 0;
+  static_assert(P::BYTES <= LDS_LIMIT, "transposed-read backward tile does not fit LDS");
+  const int cap = 8 / NW < 2 ? 8 / NW : 2;  // the kernels hold 130-250 VGPRs: two waves per SIMD
+  return launch_persistent<mlp_lp_bwd_tr_kernel<T, K0, H, NH, TS, X16>>(a, (a.N + TS - 1) / TS, P::BYTES, cap, NW * 64, st,
+                                                                        "mlp_bwd (16-bit operands, transposed reads)");
 }
 
 template <typename T, int K0, int H, int NH>
 static int launch_b(const MlpArgs& a, bool bwd, hipStream_t st) {
+  constexpr int NT = waves_b<H>() * 64;
+  if (!bwd) {
+    constexpr int TS = (H <= 64 && NH == 1) ? 64 : 32;
+    return launch_persistent<mlp_lp_fwd_kernel<T, K0, H, NH, TS>>(a, (a.N + TS - 1) / TS, PlanF<K0, H, NH, TS>::BYTES, 4, NT, st, "mlp_fwd (16-bit operands)");
+  }
+  if (a.x16) {
+    // built for the sigma_net shapes (d_in = 32 n_scales -> 128 -> 16): what the fused field forward hands over
+    if constexpr (H == 128 && NH == 1) {
+      SNERF_REQUIRE(a.d0 == K0 && a.ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0,
+                    "mlp_bwd_x16: needs d_in a multiple of 32 (%d), ldx a multiple of 8 (%d) and a 16-byte aligned X", a.d0, a.ldx);
+      // 64-sample tiles where they fit (the 160 -> 128 net of the preset: 146 KB; the 16-bit X prefetch is small enough for the registers,
+      // the fp32 one below is not: 93 spilled VGPRs); one workgroup per CU
+      constexpr int TS = PlanB<K0, H, NH, 64>::BYTES <= LDS_LIMIT ? 64 : 32;
+      using P = PlanB<K0, H, NH, TS>;
+      static_assert(P::BYTES <= LDS_LIMIT, "bf16 backward tile does not fit LDS");
+      const int64_t n_tiles = (a.N + TS - 1) / TS;
+      if (a.G) return launch_persistent<mlp_lp_bwd_kernel<T, K0, H, NH, TS, true, true>>(a, n_tiles, P::BYTES, 1, NT, st, "mlp_bwd (16-bit operands)");
+      return launch_persistent<mlp_lp_bwd_kernel<T, K0, H, NH, TS, true>>(a, n_tiles, P::BYTES, 1, NT, st, "mlp_bwd (16-bit operands)");
+    } else {
+      set_error("mlp_bwd_x16: 16-bit inputs are built for the d_in -> 128 -> d_out one-hidden-layer shapes (sigma_net), got hidden=%d n_hidden=%d", H, NH);
+      return SNERF_ERR_UNSUPPORTED;
+    }
+  }
   // 64-wide nets (color_net, the proposal nets, NeRFPlayer's heads): the transposed-read kernel (color_net 0.149 -> 0.123 ms, proposal nets
   // 0.140 -> 0.124).  128-wide nets (sigma_net) stay on the two-image kernel: their time goes into the layer-0 weight gradient and the input
   // gradient over a 160-wide input, which read more and write less -- 0.142 ms against 0.147 (64-sample tiles) / 0.152 (128) transposed.
   if constexpr (H <= 64) {
-    if (bwd) {
-      if (a.x16) {
-        set_error("mlp_bwd_x16: 16-bit inputs are built for the d_in -> 128 -> d_out one-hidden-layer shapes (sigma_net), got hidden=%d n_hidden=%d", H, NH);
-        return SNERF_ERR_UNSUPPORTED;
-      }
-      return launch_b_tr<T, K0, H, NH, false>(a, st);
-    }
-  }
-  if constexpr (H > 64) if (bwd) {
+    return launch_b_tr<T, K0, H, NH, false>(a, st);
+  } else {
     constexpr int TS = 32;
     using P = PlanB<K0, H, NH, TS>;
-    static_assert(P::BYTES <= LDS_LIMIT_B, "bf16 backward tile does not fit LDS");
-    int64_t n_tiles = (a.N + TS - 1) / TS;
-    int per_cu = (int)(LDS_LIMIT_B / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    if (a.x16) {
-      // built for the sigma_net shapes (d_in = 32 n_scales -> 128 -> 16): what the fused field forward hands over
-      if constexpr (H == 128 && NH == 1) {
-        SNERF_REQUIRE(a.d0 == K0 && a.ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0,
-                      "mlp_bwd_x16: needs d_in a multiple of 32 (%d), ldx a multiple of 8 (%d) and a 16-byte aligned X", a.d0, a.ldx);
-        // 64-sample tiles where they fit (the 160 -> 128 net of the preset: 146 KB; the 16-bit X prefetch is small enough for the registers,
-        // the fp32 one below is not: 93 spilled VGPRs)
-        constexpr int TS16 = PlanB<K0, H, NH, 64>::BYTES <= LDS_LIMIT_B ? 64 : 32;
-        using P16 = PlanB<K0, H, NH, TS16>;
-        n_tiles = (a.N + TS16 - 1) / TS16;
-        grid = n_tiles < 256 ? n_tiles : 256;
-        if (a.G) {
-          auto k = mlp_lp_bwd_kernel<T, K0, H, NH, TS16, true, true>;
-          SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-          hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_b<H>() * 64), P16::BYTES, st, a, n_tiles);
-        } else {
-          auto k = mlp_lp_bwd_kernel<T, K0, H, NH, TS16, true>;
-          SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-          hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_b<H>() * 64), P16::BYTES, st, a, n_tiles);
-        }
-      } else {
-        set_error("mlp_bwd_x16: 16-bit inputs are built for the d_in -> 128 -> d_out one-hidden-layer shapes (sigma_net), got hidden=%d n_hidden=%d", H, NH);
-        return SNERF_ERR_UNSUPPORTED;
-      }
-    } else {
-      auto k = mlp_lp_bwd_kernel<T, K0, H, NH, TS>;
-      SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-      hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_b<H>() * 64), P::BYTES, st, a, n_tiles);
-    }
-    SNERF_LAUNCH_CHECK("mlp_bwd (16-bit operands)");
-    return 0;
+    static_assert(P::BYTES <= LDS_LIMIT, "bf16 backward tile does not fit LDS");
+    return launch_persistent<mlp_lp_bwd_kernel<T, K0, H, NH, TS>>(a, (a.N + TS - 1) / TS, P::BYTES, 4, NT, st, "mlp_bwd (16-bit operands)");
   }
-  {
-    constexpr int TS = (H <= 64 && NH == 1) ? 64 : 32;
-    using P = PlanF<K0, H, NH, TS>;
-    const int64_t n_tiles = (a.N + TS - 1) / TS;
-    int per_cu = (int)(LDS_LIMIT_B / P::BYTES);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    int64_t grid = 256 * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    auto k = mlp_lp_fwd_kernel<T, K0, H, NH, TS>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(waves_b<H>() * 64), P::BYTES, st, a, n_tiles);
-  }
-  SNERF_LAUNCH_CHECK("mlp_fwd (16-bit operands)");
-  return 0;
 }
 
 // (input width padded to 32, hidden width, hidden layers)
@@ -993,23 +935,15 @@ bool mlp_bf16_supported(const snerf_mlp_desc* d) {
   return false;
 }
 
-// wave-owns-rows backward of the 64-wide nets (mlp_rows.hip)
-bool mlp_rows_supported(const snerf_mlp_desc* d, const void* args);
-int mlp_rows_dispatch(const snerf_mlp_desc* d, const void* args, hipStream_t st);
-
-// wave-owns-rows backward of sigma_net (mlp_rows128.hip)
-bool mlp_rows128_supported(const snerf_mlp_desc* d, const void* args);
-int mlp_rows128_dispatch(const snerf_mlp_desc* d, const void* args, hipStream_t st);
 // SNERF_MLP_SIGMA_ROWS=0: dev A-B switch back to the workgroup-tile kernel for sigma_net's 16-bit-input backward (read per call)
 static bool sigma_rows_off() {
   const char* e = getenv("SNERF_MLP_SIGMA_ROWS");
   return e && atoi(e) == 0;
 }
 
-int mlp_bf16_dispatch(const snerf_mlp_desc* d, const void* args, bool bwd, hipStream_t st) {
-  const MlpArgs& a = *static_cast<const MlpArgs*>(args);
-  if (bwd && a.variant == 0 && mlp_rows_supported(d, args)) return mlp_rows_dispatch(d, args, st);
-  if (bwd && a.variant == 0 && !a.gWfx && mlp_rows128_supported(d, args) && !sigma_rows_off()) return mlp_rows128_dispatch(d, args, st);
+int mlp_bf16_dispatch(const snerf_mlp_desc* d, const MlpArgs& a, bool bwd, hipStream_t st) {
+  if (bwd && a.variant == 0 && mlp_rows_supported(d, a)) return mlp_rows_dispatch(d, a, st);
+  if (bwd && a.variant == 0 && !a.gWfx && mlp_rows128_supported(d, a) && !sigma_rows_off()) return mlp_rows128_dispatch(d, a, st);
   const int k0 = (d->d_in + 31) / 32 * 32;
 #define CASE(K0, H, NH)                                                                   \
   if (k0 == K0 && d->hidden == H && d->n_hidden == NH)                                    \

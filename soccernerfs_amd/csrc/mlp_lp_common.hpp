@@ -1,11 +1,11 @@
 // Building blocks shared by the 16-bit-operand MLP kernels (mlp_lp.hip) and the fused K-Planes field kernels (field_fused.hip):
 // operand types, the "both operands row-major along the contraction index" MFMA helper, accumulator -> LDS stores, weight staging.
+// (The argument block MlpArgs, gw_add and the launch helper: mlp_args.hpp.)
 #pragma once
-#include "common.hpp"
+#include "mlp_args.hpp"
 
 namespace snerf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16;
 typedef _Float16 fp16;
 
@@ -30,42 +30,6 @@ struct Ops<fp16> {
   static __device__ __forceinline__ fp16 cvtg(float x) { return (fp16)fminf(fmaxf(x, -65504.f), 65504.f); }
 };
 
-struct MlpArgs {  // same fields as mlp.hip's (filled there)
-  const float* X; int64_t N; int ldx; int d0;
-  const float* W; int woff[4];
-  int dout;
-  float* Y; int ldy;
-  int hidden_act, out_act;
-  int aux_col; float* aux_out;
-  const float* gY; int ldgy;
-  const float* gaux;
-  float* gX; int ldgx;
-  float* gW;
-  long long* gWfx;  // deterministic mode: weight gradients accumulate here as fixed point instead (common.hpp)
-  int x16;          // X holds the 16-bit operand type (what snerf_kplanes_field_fwd wrote), not fp32: 16-bit kernels only
-  // quotient epilogue of the backward (snerf_mlp_bwd_x16_quotient; 16-bit kernels, one hidden layer of 128): instead of gX the kernel writes
-  // G = gX .* X (X = the 16-bit tile it holds in LDS) and lists the elements whose X vanished while gX did not (common.hpp: fix_append)
-  float* G; int ldg;
-  int32_t* fix_list; int fix_capacity;
-  int32_t* fix_count; int32_t* fix_count_next;
-  int variant;      // backward only: 0 = the default kernel for the shape, 1 = the workgroup-tile kernels of mlp_lp.hip (snerf_mlp_bwd_tile: A-B, cross-check)
-  // weight-gradient workspace (snerf_mlp_bwd_ws; 16-bit kernels): ws_rep replicas of the flat gradient, ws_stride floats apart.  Workgroup b adds
-  // into replica b % ws_rep instead of gW, so an address collects grid / ws_rep same-address atomics instead of one per workgroup (256 of
-  // them took ~25 us at the end of every launch, whatever the element count); snerf_mlp_gw_reduce folds the replicas into gW later.
-  float* ws; int ws_rep; int64_t ws_stride;
-  // view-dependent colour backward (snerf_kplanes_color_bwd_vd, mlp_rows.hip): X = [SH4 of the ray direction | h[:, :15]] is formed in the
-  // kernel from the per-ray directions [N / S, 3] and h (X above, row stride ldx = 16)
-  const float* dirs; int S;
-};
-
-__device__ __forceinline__ void gw_add(const MlpArgs& a, int64_t idx, float v) {
-  if (a.gWfx) fx_atomic_add(a.gWfx + idx, v);
-  else if (a.ws) atomicAdd(a.ws + (int64_t)(blockIdx.x % (unsigned)a.ws_rep) * a.ws_stride + idx, v);
-  else atomicAdd(a.gW + idx, v);
-}
-constexpr int GW_REPLICAS = 16;  // replicas of a snerf_mlp_bwd_ws workspace
-
-constexpr int LDS_LIMIT_B = 160 * 1024;
 __host__ __device__ constexpr int ldb(int k) { return k + 8; }
 
 template <typename T>

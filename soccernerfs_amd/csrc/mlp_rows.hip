@@ -530,13 +530,13 @@ __global__ __launch_bounds__(ROWS_NW * 64) void mlp_rows_bwd_kernel(MlpArgs a, i
 template <typename T, int K0P, int H, int NH, bool VD = false>
 static int launch_rows(const MlpArgs& a, hipStream_t st) {
   using P = PlanR<K0P, H, NH>;
-  static_assert(P::BYTES <= LDS_LIMIT_B, "rows backward does not fit LDS");
+  static_assert(P::BYTES <= LDS_LIMIT, "rows backward does not fit LDS");
   const int64_t n_pairs = (a.N + 31) / 32;
   int64_t grid = (n_pairs + P::NW - 1) / P::NW;
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   auto k = mlp_rows_bwd_kernel<T, K0P, H, NH, VD>;
-  SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+  SNERF_ALLOW_LDS(k, LDS_LIMIT);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(P::NW * 64), P::BYTES, st, a, n_pairs);
   SNERF_LAUNCH_CHECK("mlp_bwd (16-bit operands, wave-owns-rows)");
   return 0;
@@ -544,8 +544,7 @@ static int launch_rows(const MlpArgs& a, hipStream_t st) {
 
 // shapes served: 64 hidden units, fp32 X in float4-granular rows; one hidden layer with inputs up to 64 wide, two hidden layers with inputs up to 16 wide (the
 // 64 x 64 weight-gradient accumulator of the second hidden layer leaves no registers for a wider layer 0: 100-220 spilled VGPRs measured)
-bool mlp_rows_supported(const snerf_mlp_desc* d, const void* args) {
-  const MlpArgs& a = *static_cast<const MlpArgs*>(args);
+bool mlp_rows_supported(const snerf_mlp_desc* d, const MlpArgs& a) {
   if (d->hidden != 64 || d->d_out > 16 || a.x16 || a.G || !(d->operands == 1 || d->operands == 2)) return false;
   // X is fetched as whole float4s, unconditionally (the kernel's prefetch has no guarded loads): rows must be float4-granular and aligned;
   // anything else takes the workgroup-tile kernel
@@ -553,8 +552,7 @@ bool mlp_rows_supported(const snerf_mlp_desc* d, const void* args) {
   return (d->n_hidden == 1 && d->d_in <= 64) || (d->n_hidden == 2 && d->d_in <= 16);
 }
 
-int mlp_rows_dispatch(const snerf_mlp_desc* d, const void* args, hipStream_t st) {
-  const MlpArgs& a = *static_cast<const MlpArgs*>(args);
+int mlp_rows_dispatch(const snerf_mlp_desc* d, const MlpArgs& a, hipStream_t st) {
   const int k0 = d->d_in <= 16 ? 16 : (d->d_in <= 32 ? 32 : 64);
 #define CASE(K0P, NH)                              \
   if (k0 == K0P && d->n_hidden == NH)              \

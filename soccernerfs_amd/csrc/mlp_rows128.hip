@@ -339,16 +339,16 @@ __global__ __launch_bounds__(NW * 64) void sigma_bwd_kernel(MlpArgs a, int64_t n
 template <typename T, int K0>
 static int launch(const MlpArgs& a, hipStream_t st) {
   using P = Plan<K0>;
-  static_assert(P::BYTES <= LDS_LIMIT_B, "sigma backward (rows) does not fit LDS");
+  static_assert(P::BYTES <= LDS_LIMIT, "sigma backward (rows) does not fit LDS");
   const int64_t n_tiles = (a.N + TS - 1) / TS;
   int64_t grid = n_tiles < 256 ? n_tiles : 256;
   if (a.G) {
     auto k = sigma_bwd_kernel<T, K0, true>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), P::BYTES, st, a, n_tiles);
   } else {
     auto k = sigma_bwd_kernel<T, K0, false>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), P::BYTES, st, a, n_tiles);
   }
   SNERF_LAUNCH_CHECK("mlp_bwd (sigma_net, 16-bit operands, wave-owns-rows)");
@@ -359,8 +359,7 @@ static int launch(const MlpArgs& a, hipStream_t st) {
 
 // shapes served: 32 k -> 128 -> d_out <= 16, one hidden layer, X in the operand type (what snerf_kplanes_field_fwd writes) in 16-byte-granular rows,
 // gY rows of whole float4s
-bool mlp_rows128_supported(const snerf_mlp_desc* d, const void* args) {
-  const MlpArgs& a = *static_cast<const MlpArgs*>(args);
+bool mlp_rows128_supported(const snerf_mlp_desc* d, const MlpArgs& a) {
   if (d->hidden != 128 || d->n_hidden != 1 || d->d_in % 32 != 0 || d->d_in > 192 || d->d_out > 16 || !(d->operands == 1 || d->operands == 2)) return false;
   if (!a.x16 || (a.ldx & 7) != 0 || (reinterpret_cast<uintptr_t>(a.X) & 15) != 0) return false;
   if (a.gY && ((a.ldgy & 3) != 0 || a.ldgy < 16 || (reinterpret_cast<uintptr_t>(a.gY) & 15) != 0)) return false;
@@ -368,8 +367,7 @@ bool mlp_rows128_supported(const snerf_mlp_desc* d, const void* args) {
   return true;
 }
 
-int mlp_rows128_dispatch(const snerf_mlp_desc* d, const void* args, hipStream_t st) {
-  const MlpArgs& a = *static_cast<const MlpArgs*>(args);
+int mlp_rows128_dispatch(const snerf_mlp_desc* d, const MlpArgs& a, hipStream_t st) {
 #define CASE(K0) \
   if (d->d_in == K0) return d->operands == 2 ? r128::launch<fp16, K0>(a, st) : r128::launch<bf16, K0>(a, st);
   CASE(32) CASE(64) CASE(96) CASE(128) CASE(160) CASE(192)

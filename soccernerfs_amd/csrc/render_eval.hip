@@ -180,17 +180,17 @@ template <typename T, int NS>
 static int launch_field_render(const FieldArgs& a, int R, const RayOut& o, hipStream_t st, bool vd) {
   using P = PlanFF<NS>;
   constexpr size_t BYTES = P::BYTES + RAY_LDS_B;
-  int per_cu = (int)(LDS_LIMIT_B / BYTES);
+  int per_cu = (int)(LDS_LIMIT / BYTES);
   per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // two 8-wave workgroups per CU, as field_fwd_kernel
   int grid = 256 * per_cu;
   if (grid > R) grid = R;
   if (vd) {
     auto k = field_render_kernel<T, NS, true>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
   } else {
     auto k = field_render_kernel<T, NS, false>;
-    SNERF_ALLOW_LDS(k, LDS_LIMIT_B);
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
   }
   SNERF_LAUNCH_CHECK("kplanes_field_render");

@@ -33,7 +33,10 @@ typedef void* snerf_stream_t; /* hipStream_t */
 #define SNERF_ABI_VERSION 16
 /* Additions that leave every ABI-16 entry point and struct as it was count a REVISION instead of a new version, so that callers pinned to
  * version 16 keep loading.  Revision 1: snerf_raygen_frame, snerf_kplanes_field_render(_supported), snerf_abi_revision itself.
- * Revision 2: snerf_raygen_lens, snerf_raygen_frame_lens (rays through the cameras' OpenCV lens distortion). */
+ * Revision 2: snerf_raygen_lens, snerf_raygen_frame_lens (rays through the cameras' OpenCV lens distortion).
+ * Revision 2's surface also holds snerf_raygen_cam, snerf_raygen_frame_cam and snerf_sample_pixels_sphere (fisheye and equirectangular
+ * cameras), added WITHOUT counting a revision: callers and tests pin revision 2.  The binding lists them among the symbols it requires, so a
+ * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call. */
 #define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
@@ -622,11 +625,88 @@ typedef struct {
 } snerf_raygen_frame_lens_args;
 int snerf_raygen_frame_lens(const snerf_raygen_frame_lens_args* args, snerf_stream_t stream);
 
+/* Camera types: the values of the reference's CameraType enum (NS/cameras/cameras.py:42-47). */
+#define SNERF_CAMERA_PERSPECTIVE 1
+#define SNERF_CAMERA_FISHEYE 2
+#define SNERF_CAMERA_EQUIRECTANGULAR 3
+
+/* ABI 16 revision 2 (added to its surface, see SNERF_ABI_REVISION): snerf_raygen_lens for a table of any camera types, as
+ * Cameras._generate_rays_from_coords handles them in one function (NS/cameras/cameras.py:645-700).  The three coordinate pairs of a ray are
+ * formed and undistorted as in snerf_raygen_lens -- except for an equirectangular camera, whose row is ignored (:645-647), and when distortion
+ * is NULL (no lens) -- and each is mapped to a camera-space direction by the ray's camera's type:
+ *   perspective     (x, y, -1)                                                                    (:665-670)
+ *   fisheye         theta = clip(sqrt(x^2 + y^2), 0, pi): (x sin(theta) / theta, y sin(theta) / theta, -cos(theta))   (:672-683)
+ *   equirectangular theta = -pi x, phi = pi (0.5 - y): (-sin(theta) sin(phi), cos(phi), -cos(theta) sin(phi))         (:685-696)
+ * then rotation, normalisation, pixel area, times and the collider follow snerf_raygen (:704-741).  ONE deliberate deviation: a fisheye pair
+ * with theta == 0 (a pixel centre exactly on the principal point) gives the limit (0, 0, -1), sin(theta) / theta := 1, where the reference
+ * computes 0 * 0 / 0 = NaN.
+ * The fields are snerf_raygen_lens_args' (a prefix, unchanged) followed by the types: camera_type_stride 1 = an int32 [M] table, 0 = one value
+ * shared by all cameras; camera_type NULL = all perspective.  With every type 1 the outputs equal snerf_raygen_lens (or snerf_raygen when
+ * distortion is NULL) bit for bit.  The KERNEL TREATS A VALUE OUTSIDE 1..3 AS PERSPECTIVE: the table lives on the device, so the caller checks
+ * it before the launch (the Python binding does, where the reference raises at :698-700). */
+typedef struct {
+  const int64_t* indices;
+  const float* fx; const float* fy; const float* cx; const float* cy; /* [M] */
+  const float* c2w;        /* [M,3,4] */
+  const float* cam_times;  /* [M] or NULL */
+  int32_t R;
+  int32_t collide;
+  int32_t training;
+  float near_plane;
+  float aabb_min[3];
+  float aabb_max[3];
+  float* origins;          /* [R,3] */
+  float* dirs;             /* [R,3] */
+  float* pixel_area;       /* [R] */
+  float* dir_norm;         /* [R] */
+  float* times;            /* [R] or NULL */
+  float* nears;            /* [R] */
+  float* fars;             /* [R] */
+  const float* distortion; /* [M,6] (stride 6), [6] (stride 0) or NULL (no lens) */
+  int32_t distortion_stride;
+  const int32_t* camera_type; /* [M] (stride 1), [1] (stride 0) or NULL (all perspective) */
+  int32_t camera_type_stride;
+} snerf_raygen_cam_args;
+int snerf_raygen_cam(const snerf_raygen_cam_args* args, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface): snerf_raygen_frame_lens for ONE camera of any type: the fields of snerf_raygen_frame_lens_args
+ * (a prefix, unchanged) followed by the camera's type and whether `distortion` holds a lens row (0: no lens, the row is not read).  Every
+ * output equals snerf_raygen_cam on the meshgrid index table bit for bit; with camera_type 1 it equals snerf_raygen_frame_lens
+ * (has_distortion 1) or snerf_raygen_frame (0).  A camera_type outside 1..3 is SNERF_ERR_ARG, as NS/cameras/cameras.py:698-700 raises. */
+typedef struct {
+  float fx, fy, cx, cy;
+  float c2w[12];           /* [3,4] row-major */
+  float time;
+  int32_t W, H;
+  int32_t _pad;
+  int64_t p0, p1;
+  float near_plane;
+  float aabb_min[3];
+  float aabb_max[3];
+  float* origins;          /* [p1 - p0, 3] */
+  float* dirs;             /* [p1 - p0, 3] */
+  float* pixel_area;       /* [p1 - p0] */
+  float* dir_norm;         /* [p1 - p0] */
+  float* times;            /* [p1 - p0] or NULL */
+  float* nears;            /* [p1 - p0] */
+  float* fars;             /* [p1 - p0] */
+  float distortion[6];
+  int32_t camera_type;     /* SNERF_CAMERA_* */
+  int32_t has_distortion;
+} snerf_raygen_frame_cam_args;
+int snerf_raygen_frame_cam(const snerf_raygen_frame_cam_args* args, snerf_stream_t stream);
+
 /* PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77): indices[R,3] = floor(u[R,3] * (M,H,W)) as int64 (image, row, col), fused
  * with collate_image_dataset_batch's gather (:111-123): target[R,3] = images[c,y,x,:] / 255 for a resident uint8 image cache
  * [M,H,W,3] (images may be NULL: indices only). */
 int snerf_sample_pixels_uniform(const float* u, int32_t R, int32_t M, int32_t H, int32_t W, const uint8_t* images, int64_t* indices,
                                 float* target, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface): EquirectangularPixelSampler.sample_method (NS/data/pixel_samplers.py:255-265), the draw that is
+ * uniform on the sphere of an equirectangular image: indices[R,3] = floor((u0, acos(1 - 2 u1) / pi, u2) * (M,H,W)) as int64, in float32 as the
+ * reference evaluates it, with snerf_sample_pixels_uniform's argument list and its fused gather. */
+int snerf_sample_pixels_sphere(const float* u, int32_t R, int32_t M, int32_t H, int32_t W, const uint8_t* images, int64_t* indices,
+                               float* target, snerf_stream_t stream);
 
 /* The ray batch in order of a per-image key (image_key[M] in [0, n_keys): the rank of the image's frame time).  A batch is a set (losses are
  * means over it, the per-ray draws are i.i.d.), so its order is free; with equal-time rays adjacent, the gathers of every plane that holds the

@@ -110,6 +110,18 @@ class RaygenFrameLensArgs(C.Structure):
     _fields_ = RaygenFrameArgs._fields_ + [("distortion", C.c_float * 6)]
 
 
+class RaygenCamArgs(C.Structure):
+    """snerf_raygen_cam_args (added to ABI 16 revision 2, csrc/raygen.hip): RaygenLensArgs' fields, then the camera-type table and its stride
+    (1: int32 [M], 0: one shared value); distortion and camera_type may be null."""
+    _fields_ = RaygenLensArgs._fields_ + [("camera_type", C.c_void_p), ("camera_type_stride", C.c_int32)]
+
+
+class RaygenFrameCamArgs(C.Structure):
+    """snerf_raygen_frame_cam_args (added to ABI 16 revision 2, csrc/render_eval.hip): RaygenFrameLensArgs' fields, then the camera's type (1..3)
+    and whether the distortion row is a lens (0: it is not read)."""
+    _fields_ = RaygenFrameLensArgs._fields_ + [("camera_type", C.c_int32), ("has_distortion", C.c_int32)]
+
+
 class TgridDesc(C.Structure):
     _fields_ = [("D", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("grid_C", C.c_int32), ("H", C.c_int32), ("gridtype", C.c_int32),
                 ("align_corners", C.c_int32), ("S", C.c_float), ("offsets", C.c_int32 * 33)]
@@ -146,6 +158,10 @@ def lib():
             "Build it with `python -m soccernerfs_amd.build` (or __graft_entry__.build())."
         )
     l = C.CDLL(LIB_PATH)
+    # entries added to revision 2's surface without a new revision number: a library from before them must fail here, not at the first call
+    missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere") if not hasattr(l, s)]
+    if missing:
+        raise RuntimeError(f"libsnerf at {LIB_PATH} lacks {', '.join(missing)} (ABI {ABI_VERSION} revision {ABI_REVISION}): rebuild the library")
     l.snerf_last_error.restype = C.c_char_p
     l.snerf_target_arch.restype = C.c_char_p
     l.snerf_mlp_param_count.restype = C.c_int64
@@ -170,6 +186,7 @@ def lib():
     l.snerf_render_bwd.argtypes = [P, P, P, I, P, P, I, I, P, P, I, P]
     l.snerf_render_mse_bwd.argtypes = [P, P, P, I, P, P, F, I, I, P, P, P, P]
     l.snerf_sample_pixels_uniform.argtypes = [P, I, I, I, I, P, P, P, P]
+    l.snerf_sample_pixels_sphere.argtypes = [P, I, I, I, I, P, P, P, P]
     l.snerf_sort_rays_by_key.argtypes = [P, P, I, I, P, I, P, P, P]
     l.snerf_trunc_exp_fwd.argtypes = [P, L, P, P]
     l.snerf_trunc_exp_bwd.argtypes = [P, P, L, P, P]
@@ -195,6 +212,8 @@ def lib():
     l.snerf_kplanes_field_render.argtypes = [P, P, P, I, P, P, P, P, F, P, P, P, P, P, P, P]
     l.snerf_raygen_lens.argtypes = [P, P]
     l.snerf_raygen_frame_lens.argtypes = [P, P]
+    l.snerf_raygen_cam.argtypes = [P, P]
+    l.snerf_raygen_frame_cam.argtypes = [P, P]
     if l.snerf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
     revision = l.snerf_abi_revision() if hasattr(l, "snerf_abi_revision") else 0  # a library from before revisions were counted
@@ -249,12 +268,15 @@ EXPORTS = [
     "snerf_isg_maps",
     "snerf_adam_step_tv",
     "snerf_sample_pixels_uniform",
+    "snerf_sample_pixels_sphere",
     "snerf_sort_rays_by_key",
     "snerf_kplanes_scatter_sorted_scales",
     "snerf_raygen",
     "snerf_raygen_frame",
     "snerf_raygen_lens",
     "snerf_raygen_frame_lens",
+    "snerf_raygen_cam",
+    "snerf_raygen_frame_cam",
     "snerf_aabb_collide",
     "snerf_tgrid_encode_fwd",
     "snerf_hashgrid_layout",

@@ -1,4 +1,5 @@
-// Ray generation (pinhole, or through the OpenCV lens distortion; camera optimiser off) fused with the AABB collider.
+// Ray generation (pinhole, through the OpenCV lens distortion, or by camera type: perspective / fisheye / equirectangular; camera optimiser
+// off) fused with the AABB collider.
 //
 // Reference: RayGenerator.forward (NS/model_components/ray_generators.py:41-59) ->
 // Cameras._generate_rays_from_coords (NS/cameras/cameras.py:505-741; the perspective slice :596-633,:663-670,
@@ -62,6 +63,34 @@ __global__ void raygen_lens_kernel(RaygenLensArgs l) {
   if (a.collide) aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, a.training, a.nears[r], a.fars[r]);
 }
 
+// raygen_lens_kernel for a table of any camera types (Cameras._generate_rays_from_coords, cameras.py:645-700): each ray branches on ITS camera's
+// type -- a mixed table is legal in the reference, and the lanes of a wavefront may diverge here.  Another sibling: the two kernels above stay
+// the code they were.  camera_type: int32 [M] (stride 1), one shared value (stride 0) or null (all perspective); distortion may be null (no lens).
+struct RaygenCamArgs {
+  RaygenLensArgs lens;
+  const int32_t* camera_type;
+  int camera_type_stride;
+};
+
+__global__ void raygen_cam_kernel(RaygenCamArgs q) {
+  const RaygenArgs& a = q.lens.base;
+  int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.R) return;
+  const int64_t c = a.indices[(int64_t)r * 3], yi = a.indices[(int64_t)r * 3 + 1], xi = a.indices[(int64_t)r * 3 + 2];
+  const int type = q.camera_type ? q.camera_type[c * q.camera_type_stride] : CAMERA_PERSPECTIVE;
+  const bool lens = q.lens.distortion != nullptr;
+  float k[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) k[i] = lens ? q.lens.distortion[c * q.lens.distortion_stride + i] : 0.f;
+  const PixelRay p = pixel_ray_cam(yi, xi, a.fx[c], a.fy[c], a.cx[c], a.cy[c], a.c2w + c * 12, type, lens, k);
+#pragma unroll
+  for (int k3 = 0; k3 < 3; ++k3) { a.origins[(int64_t)r * 3 + k3] = p.o[k3]; a.dirs[(int64_t)r * 3 + k3] = p.d[k3]; }
+  a.pixel_area[r] = p.pixel_area;
+  a.dir_norm[r] = p.dir_norm;
+  if (a.times) a.times[r] = a.cam_times ? a.cam_times[c] : 0.f;
+  if (a.collide) aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, a.training, a.nears[r], a.fars[r]);
+}
+
 // PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77: floor(rand(R,3) * [M,H,W]).long()) fused with the image gather of
 // collate_image_dataset_batch (:111-123): one lane per ray instead of seven elementwise / index launches
 __global__ void sample_pixels_kernel(const float* __restrict__ u, int R, int M, int H, int W, const uint8_t* __restrict__ images,
@@ -77,6 +106,25 @@ __global__ void sample_pixels_kernel(const float* __restrict__ u, int R, int M, 
     const uint8_t* px = images + (((int64_t)c * H + y) * W + x) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) target[(int64_t)r * 3 + k] = (float)px[k] / 255.0f;  // uint8 -> float32 / 255 (NS/data/datasets/base_dataset.py:82)
+  }
+}
+
+// EquirectangularPixelSampler.sample_method (pixel_samplers.py:255-265): the draw that is uniform on the sphere of an equirectangular image --
+// image and column as above, the row by inverse-transform sampling of f(phi) = sin(phi) / 2: floor((acos(1 - 2 u1) / pi) * H), in float32 with
+// every operation rounded as torch rounds it -- with sample_pixels_kernel's gather.  u1 < 1 keeps acos below pi; the clamp is the same guard.
+__global__ void sample_pixels_sphere_kernel(const float* __restrict__ u, int R, int M, int H, int W, const uint8_t* __restrict__ images,
+                                            int64_t* __restrict__ indices, float* __restrict__ target) {
+  int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float phi = acosf(1.0f - 2.0f * u[(int64_t)r * 3 + 1]) / PI_F32;
+  int64_t c = (int64_t)floorf(u[(int64_t)r * 3] * (float)M), y = (int64_t)floorf(phi * (float)H), x = (int64_t)floorf(u[(int64_t)r * 3 + 2] * (float)W);
+  c = c < M ? c : M - 1; y = y < H ? y : H - 1; x = x < W ? x : W - 1;
+  y = y < 0 ? 0 : y;  // u1 outside [0, 1] (not a rand() value) makes acos NaN: keep the gather inside the image
+  indices[(int64_t)r * 3] = c; indices[(int64_t)r * 3 + 1] = y; indices[(int64_t)r * 3 + 2] = x;
+  if (images) {
+    const uint8_t* px = images + (((int64_t)c * H + y) * W + x) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) target[(int64_t)r * 3 + k] = (float)px[k] / 255.0f;
   }
 }
 
@@ -171,6 +219,41 @@ extern "C" int snerf_raygen_lens(const snerf_raygen_lens_args* p, snerf_stream_t
   l.distortion = p->distortion; l.distortion_stride = p->distortion_stride;
   hipLaunchKernelGGL(raygen_lens_kernel, dim3(ceil_div(p->R, 256)), dim3(256), 0, (hipStream_t)stream, l);
   SNERF_LAUNCH_CHECK("raygen_lens");
+  return 0;
+}
+
+extern "C" int snerf_raygen_cam(const snerf_raygen_cam_args* p, snerf_stream_t stream) {
+  SNERF_REQUIRE(p, "raygen_cam: null args");
+  SNERF_REQUIRE(p->R >= 0, "raygen_cam: R=%d", p->R);
+  SNERF_REQUIRE(p->distortion_stride == 0 || p->distortion_stride == 6, "raygen_cam: distortion_stride=%d (0: one shared row, 6: a [M,6] table)",
+                p->distortion_stride);
+  SNERF_REQUIRE(p->camera_type_stride == 0 || p->camera_type_stride == 1, "raygen_cam: camera_type_stride=%d (0: one shared value, 1: an [M] table)",
+                p->camera_type_stride);
+  if (p->R == 0) return 0;
+  SNERF_REQUIRE(p->indices && p->fx && p->fy && p->cx && p->cy && p->c2w, "raygen_cam: null camera/index buffer");
+  SNERF_REQUIRE(p->origins && p->dirs && p->pixel_area && p->dir_norm, "raygen_cam: null output buffer");
+  SNERF_REQUIRE(!p->collide || (p->nears && p->fars), "raygen_cam: collide set but nears/fars null");
+  RaygenCamArgs q;
+  RaygenArgs& a = q.lens.base;
+  a.indices = p->indices; a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy; a.c2w = p->c2w; a.cam_times = p->cam_times; a.R = p->R;
+  a.origins = p->origins; a.dirs = p->dirs; a.pixel_area = p->pixel_area; a.dir_norm = p->dir_norm; a.times = p->times;
+  a.collide = p->collide; a.training = p->training; a.near_plane = p->near_plane;
+  for (int k = 0; k < 3; ++k) { a.aabb_min[k] = p->aabb_min[k]; a.aabb_max[k] = p->aabb_max[k]; }
+  a.nears = p->nears; a.fars = p->fars;
+  q.lens.distortion = p->distortion; q.lens.distortion_stride = p->distortion_stride;
+  q.camera_type = p->camera_type; q.camera_type_stride = p->camera_type_stride;
+  hipLaunchKernelGGL(raygen_cam_kernel, dim3(ceil_div(p->R, 256)), dim3(256), 0, (hipStream_t)stream, q);
+  SNERF_LAUNCH_CHECK("raygen_cam");
+  return 0;
+}
+
+extern "C" int snerf_sample_pixels_sphere(const float* u, int32_t R, int32_t M, int32_t H, int32_t W, const uint8_t* images, int64_t* indices,
+                                          float* target, snerf_stream_t stream) {
+  SNERF_REQUIRE(R >= 0 && M >= 1 && H >= 1 && W >= 1, "sample_pixels_sphere: R=%d M=%d H=%d W=%d", R, M, H, W);
+  if (R == 0) return 0;
+  SNERF_REQUIRE(u && indices && (!images || target), "sample_pixels_sphere: null buffer");
+  hipLaunchKernelGGL(sample_pixels_sphere_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, (hipStream_t)stream, u, R, M, H, W, images, indices, target);
+  SNERF_LAUNCH_CHECK("sample_pixels_sphere");
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// One pixel's ray (pinhole, or through an OpenCV lens) and its AABB interval: the arithmetic of Cameras._generate_rays_from_coords (NS/cameras/cameras.py:596-633,
-// :663-670, :704-741) and AABBBoxCollider._intersect_with_aabb (NS/model_components/scene_colliders.py:59-95), shared by the kernel that reads
+// One pixel's ray (pinhole, through an OpenCV lens, or of a fisheye / equirectangular camera) and its AABB interval: the arithmetic of
+// Cameras._generate_rays_from_coords (NS/cameras/cameras.py:596-741) and AABBBoxCollider._intersect_with_aabb (NS/model_components/scene_colliders.py:59-95), shared by the kernel that reads
 // (camera, row, col) from an index table (raygen.hip) and the one that walks a frame's pixels in order (render_eval.hip): one copy, same bits.
 // Contraction is off inside these functions whatever the including file sets: the reference rounds every product.
 #pragma once
@@ -88,6 +88,66 @@ __device__ __forceinline__ PixelRay pixel_ray_lens(int64_t yi, int64_t xi, float
   cam_to_world(m, c[0][0], c[0][1], -1.f, p.d, p.dir_norm);
   cam_to_world(m, c[1][0], c[1][1], -1.f, dx, nx);
   cam_to_world(m, c[2][0], c[2][1], -1.f, dy, ny);
+  const float* d0 = p.d;
+  float ax = sqrtf(((d0[0] - dx[0]) * (d0[0] - dx[0]) + (d0[1] - dx[1]) * (d0[1] - dx[1])) + (d0[2] - dx[2]) * (d0[2] - dx[2]));
+  float ay = sqrtf(((d0[0] - dy[0]) * (d0[0] - dy[0]) + (d0[1] - dy[1]) * (d0[1] - dy[1])) + (d0[2] - dy[2]) * (d0[2] - dy[2]));
+  p.o[0] = m[3]; p.o[1] = m[7]; p.o[2] = m[11];
+  p.pixel_area = ax * ay;
+  return p;
+}
+
+// CameraType of NS/cameras/cameras.py:42-47 (the values of the reference's enum)
+constexpr int CAMERA_PERSPECTIVE = 1, CAMERA_FISHEYE = 2, CAMERA_EQUIRECTANGULAR = 3;
+constexpr float PI_F32 = 3.14159265358979323846f;  // math.pi / torch.pi as a float32 tensor operand holds it
+
+// One (undistorted) coordinate pair -> the ray's direction in camera coordinates, by camera type (cameras.py:663-696); every product rounded,
+// Python's left-to-right association written out.  An unknown type is treated as perspective: the callers refuse it before the launch.
+__device__ __forceinline__ void camera_direction(int type, float cx, float cy, float d[3]) {
+#pragma clang fp contract(off)
+  if (type == CAMERA_FISHEYE) {  // :672-683
+    float theta = sqrtf(cx * cx + cy * cy);
+    theta = fminf(fmaxf(theta, 0.0f), PI_F32);  // torch.clip(theta, 0.0, math.pi)
+    const float s = sinf(theta);
+    // ONE deliberate deviation: at theta == 0 (a pixel centre exactly on the principal point) the reference's x * sin(theta) / theta is
+    // 0 * 0 / 0 = NaN; here sin(theta) / theta := 1, its limit, so the ray is (0, 0, -1).  Every other input, theta clipped at pi included,
+    // is the reference's expression (x * sin(theta)) / theta.
+    d[0] = theta == 0.0f ? cx : (cx * s) / theta;
+    d[1] = theta == 0.0f ? cy : (cy * s) / theta;
+    d[2] = -cosf(theta);
+  } else if (type == CAMERA_EQUIRECTANGULAR) {  // :685-696
+    const float theta = -PI_F32 * cx;  // minus sign for right-handed
+    const float phi = PI_F32 * (0.5f - cy);
+    const float sp = sinf(phi);
+    d[0] = -sinf(theta) * sp;
+    d[1] = cosf(phi);
+    d[2] = -cosf(theta) * sp;
+  } else {  // :665-670
+    d[0] = cx; d[1] = cy; d[2] = -1.f;
+  }
+}
+
+// pixel_ray / pixel_ray_lens for a camera of any CameraType (cameras.py:620-741): the three coordinate pairs are formed as pixel_ray_lens forms
+// them; each is undistorted unless there is no lens row (lens == false: k is not read) or the camera is equirectangular ("Do not apply
+// distortion for equirectangular images", :645-647); each is mapped to its camera-space direction by type; the rest is pixel_ray's code.  For a
+// perspective camera the statements are pixel_ray's (no lens) or pixel_ray_lens's, so the outputs are the same bits.  The row comes as a flag
+// and an array, not as a nullable pointer: a pointer that may be null would put the array into scratch memory.
+__device__ __forceinline__ PixelRay pixel_ray_cam(int64_t yi, int64_t xi, float fx, float fy, float cx, float cy, const float* m, int type, bool lens,
+                                                  const float k[6]) {
+#pragma clang fp contract(off)
+  const float y = (float)yi + 0.5f, x = (float)xi + 0.5f;
+  float c[3][2] = {{(x - cx) / fx, -(y - cy) / fy}, {((x + 1.f) - cx) / fx, -(y - cy) / fy}, {(x - cx) / fx, -((y + 1.f) - cy) / fy}};
+  if (lens && type != CAMERA_EQUIRECTANGULAR) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) undistort_pair(c[i][0], c[i][1], k, c[i][0], c[i][1]);
+  }
+  float v[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) camera_direction(type, c[i][0], c[i][1], v[i]);
+  float dx[3], dy[3], nx, ny;
+  PixelRay p;
+  cam_to_world(m, v[0][0], v[0][1], v[0][2], p.d, p.dir_norm);
+  cam_to_world(m, v[1][0], v[1][1], v[1][2], dx, nx);
+  cam_to_world(m, v[2][0], v[2][1], v[2][2], dy, ny);
   const float* d0 = p.d;
   float ax = sqrtf(((d0[0] - dx[0]) * (d0[0] - dx[0]) + (d0[1] - dx[1]) * (d0[1] - dx[1])) + (d0[2] - dx[2]) * (d0[2] - dx[2]));
   float ay = sqrtf(((d0[0] - dy[0]) * (d0[0] - dy[0]) + (d0[1] - dy[1]) * (d0[1] - dy[1])) + (d0[2] - dy[2]) * (d0[2] - dy[2]));

@@ -70,6 +70,27 @@ __global__ void raygen_frame_lens_kernel(FrameRaygenLensArgs l) {
   aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, 0, a.nears[r], a.fars[r]);
 }
 
+// raygen_frame_lens_kernel for a camera of any CameraType (cameras.py:645-700): the single type goes by value, so the branch is uniform
+struct FrameRaygenCamArgs {
+  FrameRaygenLensArgs lens;
+  int camera_type, has_distortion;
+};
+
+__global__ void raygen_frame_cam_kernel(FrameRaygenCamArgs q) {
+  const FrameRaygenArgs& a = q.lens.base;
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.p1 - a.p0) return;
+  const uint32_t pix = (uint32_t)(a.p0 + r);  // W * H < 2^31 (checked by the entry point)
+  const uint32_t yi = pix / (uint32_t)a.W, xi = pix - yi * (uint32_t)a.W;
+  const PixelRay p = pixel_ray_cam((int64_t)yi, (int64_t)xi, a.fx, a.fy, a.cx, a.cy, a.c2w, q.camera_type, q.has_distortion != 0, q.lens.distortion);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { a.origins[r * 3 + k] = p.o[k]; a.dirs[r * 3 + k] = p.d[k]; }
+  a.pixel_area[r] = p.pixel_area;
+  a.dir_norm[r] = p.dir_norm;
+  if (a.times) a.times[r] = a.time;
+  aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, 0, a.nears[r], a.fars[r]);
+}
+
 struct RayOut {
   float cutoff;
   float* rgb_out; float* acc_out; float* depth_median; float* depth_expected;
@@ -238,6 +259,29 @@ extern "C" int snerf_raygen_frame_lens(const snerf_raygen_frame_lens_args* p, sn
   for (int k = 0; k < 6; ++k) l.distortion[k] = p->distortion[k];
   hipLaunchKernelGGL(raygen_frame_lens_kernel, dim3(ceil_div(p->p1 - p->p0, 256)), dim3(256), 0, (hipStream_t)stream, l);
   SNERF_LAUNCH_CHECK("raygen_frame_lens");
+  return 0;
+}
+
+extern "C" int snerf_raygen_frame_cam(const snerf_raygen_frame_cam_args* p, snerf_stream_t stream) {
+  SNERF_REQUIRE(p, "raygen_frame_cam: null args");
+  SNERF_REQUIRE(p->camera_type >= CAMERA_PERSPECTIVE && p->camera_type <= CAMERA_EQUIRECTANGULAR,
+                "raygen_frame_cam: camera_type=%d not supported (1: perspective, 2: fisheye, 3: equirectangular)", p->camera_type);
+  SNERF_REQUIRE(p->W >= 1 && p->H >= 1 && (int64_t)p->W * p->H < (1LL << 31), "raygen_frame_cam: W=%d H=%d", p->W, p->H);
+  SNERF_REQUIRE(p->p0 >= 0 && p->p0 <= p->p1 && p->p1 <= (int64_t)p->W * p->H, "raygen_frame_cam: pixel range [%lld, %lld) outside the %d x %d frame",
+                (long long)p->p0, (long long)p->p1, p->W, p->H);
+  if (p->p0 == p->p1) return 0;
+  SNERF_REQUIRE(p->origins && p->dirs && p->pixel_area && p->dir_norm && p->nears && p->fars, "raygen_frame_cam: null output buffer");
+  FrameRaygenCamArgs q;
+  FrameRaygenArgs& a = q.lens.base;
+  a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy; a.time = p->time; a.W = p->W; a.H = p->H; a.p0 = p->p0; a.p1 = p->p1;
+  for (int k = 0; k < 12; ++k) a.c2w[k] = p->c2w[k];
+  a.near_plane = p->near_plane;
+  for (int k = 0; k < 3; ++k) { a.aabb_min[k] = p->aabb_min[k]; a.aabb_max[k] = p->aabb_max[k]; }
+  a.origins = p->origins; a.dirs = p->dirs; a.pixel_area = p->pixel_area; a.dir_norm = p->dir_norm; a.times = p->times; a.nears = p->nears; a.fars = p->fars;
+  for (int k = 0; k < 6; ++k) q.lens.distortion[k] = p->distortion[k];
+  q.camera_type = p->camera_type; q.has_distortion = p->has_distortion != 0;
+  hipLaunchKernelGGL(raygen_frame_cam_kernel, dim3(ceil_div(p->p1 - p->p0, 256)), dim3(256), 0, (hipStream_t)stream, q);
+  SNERF_LAUNCH_CHECK("raygen_frame_cam");
   return 0;
 }
 

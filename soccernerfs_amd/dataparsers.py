@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .cameras import Cameras
+from .cameras import CAMERA_MODEL_TO_TYPE, Cameras, CameraType
 from .scene_colliders import SceneBox
 
 # camera name -> unique id (:44-73)
@@ -225,8 +225,14 @@ class Broadcaststyle:
         a = cfg.scene_scale
         lo = [-a, -a, -0.1] if cfg.cap_box_floor else [-a, -a, -a]
         scene_box = SceneBox(aabb=torch.tensor([lo, [a, a, a]], dtype=torch.float32))
-        if meta.get("camera_model", "OPENCV") not in ("OPENCV", "PERSPECTIVE", "PINHOLE", "SIMPLE_PINHOLE"):
-            raise NotImplementedError(f"camera model {meta['camera_model']!r}: only perspective cameras are built")
+        model = meta.get("camera_model", "OPENCV")
+        # broadcaststyle_dataparser.py:464-467 (and its siblings): the file's camera_model through CAMERA_MODEL_TO_TYPE, perspective without one
+        if model == "PERSPECTIVE":  # not in the reference's table; this parser accepted it before the table was restated, and still does
+            camera_type = CameraType.PERSPECTIVE
+        elif model in CAMERA_MODEL_TO_TYPE:
+            camera_type = CAMERA_MODEL_TO_TYPE[model]
+        else:
+            raise NotImplementedError(f"camera model {model!r}: not one of {sorted(CAMERA_MODEL_TO_TYPE)}")
         idx = torch.tensor(indices, dtype=torch.long)
         val = lambda k, dt: (dt(meta[k]) if fixed[k] else torch.tensor(per[k], dtype=torch.float32 if dt is float else torch.int32)[idx])
         fx, fy, cx, cy = val("fl_x", float), val("fl_y", float), val("cx", float), val("cy", float)
@@ -241,7 +247,7 @@ class Broadcaststyle:
                 raise NotImplementedError("cameras of different image sizes")
             height, width = int(height[0]), int(width[0])
         cameras = Cameras(camera_to_worlds=poses[idx][:, :3, :4], fx=fx, fy=fy, cx=cx, cy=cy, width=width, height=height, times=t, ids=ids,
-                          distortion_params=dist)
+                          distortion_params=dist, camera_type=camera_type)
         assert self.downscale_factor is not None
         cameras.rescale_output_resolution(1.0 / self.downscale_factor)
         return DataparserOutputs(image_filenames=sel(image_filenames), cameras=cameras, scene_box=scene_box,

@@ -775,19 +775,43 @@ def fx_to_float(fx: torch.Tensor, out: torch.Tensor, accumulate: bool = False):
     _lib.check(_lib.lib().snerf_fx_to_float(_ptr(fx), _ptr(out), fx.numel(), int(accumulate), _stream()), "fx_to_float")
 
 
-def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_plane: float = 0.0, training: bool = True, distortion_params=None):
+CAMERA_TYPES = (1, 2, 3)  # CameraType of NS/cameras/cameras.py:42-47: perspective, fisheye, equirectangular
+
+
+def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_plane: float = 0.0, training: bool = True, distortion_params=None,
+                  camera_type=None, validate_camera_type: bool = True):
     """RayGenerator.forward (+ AABBBoxCollider when aabb is given).  indices int64 [R,3]; per-camera fx,fy,cx,cy [M],
     c2w [M,3,4], cam_times [M].  Returns dict of origins, directions, pixel_area, directions_norm, times, (nears, fars).
     distortion_params: None = pinhole rays (snerf_raygen); a float32 tensor [M,6] (one OpenCV row k1 k2 k3 k4 p1 p2 per camera) or [6] (one row
-    for all cameras) = the rays through that lens (snerf_raygen_lens), as the reference's Cameras with distortion_params generates them."""
+    for all cameras) = the rays through that lens (snerf_raygen_lens), as the reference's Cameras with distortion_params generates them.
+    camera_type: None = all perspective (the two entries above, as ever); an int or a CameraType (one type for all cameras) or an integer tensor
+    [M] (one per camera, mixed tables included) = snerf_raygen_cam (cameras.py:663-700: 1 perspective, 2 fisheye, 3 equirectangular, which ignores
+    the lens rows).  A value outside 1..3 raises, as the reference does; for a device tensor that check reads it back, so a caller that has
+    checked its table on the host (Cameras does, once, in its constructor) passes validate_camera_type=False."""
     if not indices.is_cuda or indices.dtype != torch.int64:
         raise RuntimeError("generate_rays: indices must be an int64 HIP device tensor")
     indices = indices.contiguous()
     R, dev = indices.shape[0], indices.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     out = {"origins": f(R, 3), "directions": f(R, 3), "pixel_area": f(R, 1), "directions_norm": f(R, 1), "times": f(R, 1)}
-    lens = distortion_params is not None
-    a = _lib.RaygenLensArgs() if lens else _lib.RaygenArgs()
+    lens, cam = distortion_params is not None, camera_type is not None
+    a = _lib.RaygenCamArgs() if cam else _lib.RaygenLensArgs() if lens else _lib.RaygenArgs()
+    if cam:
+        M = c2w.shape[0]
+        if isinstance(camera_type, torch.Tensor):
+            if camera_type.is_floating_point() or camera_type.numel() not in (1, M):
+                raise RuntimeError(f"generate_rays: camera_type {tuple(camera_type.shape)} {camera_type.dtype}: expected an integer tensor [{M}] or one value")
+            camera_type = camera_type.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+            if validate_camera_type:
+                lo, hi = (int(v) for v in torch.aminmax(camera_type))
+                if lo < CAMERA_TYPES[0] or hi > CAMERA_TYPES[-1]:
+                    raise ValueError(f"Camera type {lo if lo < CAMERA_TYPES[0] else hi} not supported.")
+        else:
+            value = int(getattr(camera_type, "value", camera_type))
+            if value not in CAMERA_TYPES:
+                raise ValueError(f"Camera type {value} not supported.")
+            camera_type = torch.full((1,), value, dtype=torch.int32, device=dev)
+        a.camera_type, a.camera_type_stride = camera_type.data_ptr(), 1 if camera_type.numel() > 1 else 0
     if lens:
         distortion_params = _f32c(distortion_params, "distortion_params")
         if tuple(distortion_params.shape) not in ((6,), (c2w.shape[0], 6)):
@@ -808,7 +832,9 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
             a.aabb_min[k], a.aabb_max[k] = ab[0][k], ab[1][k]
         out["nears"], out["fars"] = f(R, 1), f(R, 1)
         a.nears, a.fars = out["nears"].data_ptr(), out["fars"].data_ptr()
-    if lens:
+    if cam:
+        _lib.check(_lib.lib().snerf_raygen_cam(C.byref(a), _stream()), "raygen_cam")
+    elif lens:
         _lib.check(_lib.lib().snerf_raygen_lens(C.byref(a), _stream()), "raygen_lens")
     else:
         _lib.check(_lib.lib().snerf_raygen(C.byref(a), _stream()), "raygen")
@@ -853,6 +879,22 @@ def sample_pixels_uniform(u: torch.Tensor, num_images: int, height: int, width: 
         target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
     _lib.check(_lib.lib().snerf_sample_pixels_uniform(_ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
                                                       _ptr(target) if target is not None else None, _stream()), "sample_pixels_uniform")
+    return idx, target
+
+
+def sample_pixels_sphere(u: torch.Tensor, num_images: int, height: int, width: int, images: Optional[torch.Tensor] = None):
+    """EquirectangularPixelSampler.sample_method's draw (pixel_samplers.py:255-265) from u = rand(R,3): image and column as sample_pixels_uniform,
+    the row floor(acos(1 - 2 u1) / pi * H), uniform on the sphere of an equirectangular image; the same fused gather and the same returns."""
+    u = _f32c(u, "u")
+    R = u.shape[0]
+    idx = torch.empty(R, 3, dtype=torch.int64, device=u.device)
+    target = None
+    if images is not None:
+        if not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous() or tuple(images.shape) != (num_images, height, width, 3):
+            raise RuntimeError("sample_pixels_sphere: images must be a contiguous uint8 HIP tensor [M,H,W,3]")
+        target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
+    _lib.check(_lib.lib().snerf_sample_pixels_sphere(_ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
+                                                     _ptr(target) if target is not None else None, _stream()), "sample_pixels_sphere")
     return idx, target
 
 

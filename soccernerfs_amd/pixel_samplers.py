@@ -1,4 +1,5 @@
-"""Pixel samplers with the interface of NS/data/pixel_samplers.py (PixelSampler :24-128, DynamicBasedPixelSampler :329-426)
+"""Pixel samplers with the interface of NS/data/pixel_samplers.py (PixelSampler :24-128, EquirectangularPixelSampler :228-267,
+DynamicBasedPixelSampler :329-426)
 and the IST weight maps of NS/data/datasets/dynamic_dataset.py:328-470 -- all on the device, no host loop, no sync."""
 import ctypes as C
 from math import floor
@@ -162,6 +163,18 @@ class PixelSampler:
 
     def sample(self, image_batch: Dict):
         return self.collate_image_dataset_batch(image_batch, self.num_rays_per_batch, keep_full_image=self.keep_full_image)
+
+
+class EquirectangularPixelSampler(PixelSampler):
+    """Pixels of equirectangular images drawn uniformly on the sphere (pixel_samplers.py:228-267): the row by inverse-transform sampling of
+    f(phi) = sin(phi) / 2, so that the poles are not over-sampled.  What the datamanagers switch to when every training image is
+    equirectangular (NS/data/datamanagers/dynamic_datamanager.py:104-107).  With a mask the reference falls back to the uniform draw."""
+
+    def sample_method(self, batch_size: int, num_images: int, image_height: int, image_width: int, mask=None, batch=None, device="cuda"):
+        if mask is not None:
+            return super().sample_method(batch_size, num_images, image_height, image_width, mask=mask, device=device)
+        # :259-265 floor((rand, acos(1 - 2 rand) / pi, rand) * [M,H,W]).long(), one kernel
+        return ops.sample_pixels_sphere(torch.rand((batch_size, 3), device=device), num_images, image_height, image_width)[0]
 
 
 class DynamicBasedPixelSampler(PixelSampler):

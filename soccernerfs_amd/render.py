@@ -6,7 +6,8 @@ Model.get_outputs_for_camera_ray_bundle (NS/models/base_model.py:159-186) pushes
 on the caller's stream, built for inference:
 
   1. snerf_raygen_frame            rays of the chunk's pixels (no index table) + the AABB collider; snerf_raygen_frame_lens for a camera
-                                   whose distortion row has a non-zero coefficient
+                                   whose distortion row has a non-zero coefficient, snerf_raygen_frame_cam for a fisheye or
+                                   equirectangular camera
   2. snerf_spaced_bins             the first level's bins, no jitter
   3. 2 x (snerf_kplanes_density_fwd + snerf_pdf_resample, u_mode 2)   the proposal levels, eval-mode sampler
   4. snerf_kplanes_field_fwd + snerf_weights_fwd + snerf_render_fwd, or (fused_tail=True / a transmittance cutoff) snerf_kplanes_field_render:
@@ -21,8 +22,8 @@ from typing import Dict, Optional, Sequence, Union
 import torch
 
 from . import _lib, metrics, ops
-from .camera_paths import get_path_from_json, load_camera_path
-from .cameras import Cameras
+from .camera_paths import ALL_CAMERA_TYPES, get_path_from_json, load_camera_path
+from .cameras import Cameras, CameraType
 from .fused_step import FusedStep, anneal_value
 
 
@@ -95,15 +96,16 @@ class KPlanesRenderer:
 
     # ---- cameras ----
     def _host_table(self, cameras: Cameras):
-        """fx, fy, cx, cy, c2w, times and distortion rows of a camera table as host lists (snerf_raygen_frame(_lens) takes one camera by value):
-        read back once per table."""
+        """fx, fy, cx, cy, c2w, times, distortion rows and camera types of a camera table as host lists (snerf_raygen_frame(_lens, _cam) takes
+        one camera by value): read back once per table."""
         key = id(cameras)
         hit = self._host_tables.get(key)
         if hit is None or hit[0] is not cameras:
             t = lambda x: x.detach().cpu().tolist()
             hit = (cameras, {"fx": t(cameras.fx), "fy": t(cameras.fy), "cx": t(cameras.cx), "cy": t(cameras.cy),
                              "c2w": t(cameras.camera_to_worlds.reshape(len(cameras), 12)), "times": None if cameras.times is None else t(cameras.times),
-                             "distortion": t(cameras.distortion_params) if cameras.has_distortion else None})
+                             "distortion": t(cameras.distortion_params) if cameras.has_distortion else None,
+                             "camera_type": None if cameras.all_perspective else t(cameras.camera_type)})
             self._host_tables = {key: hit}
         return hit[1]
 
@@ -118,7 +120,9 @@ class KPlanesRenderer:
         n = p1 - p0
         ra.p0, ra.p1 = p0, p1
         with self._span("raygen_frame"):
-            if isinstance(ra, _lib.RaygenFrameLensArgs):
+            if isinstance(ra, _lib.RaygenFrameCamArgs):
+                self._ck(lib.snerf_raygen_frame_cam(C.byref(ra), self._st), "raygen_frame_cam")
+            elif isinstance(ra, _lib.RaygenFrameLensArgs):
                 self._ck(lib.snerf_raygen_frame_lens(C.byref(ra), self._st), "raygen_frame_lens")
             else:
                 self._ck(lib.snerf_raygen_frame(C.byref(ra), self._st), "raygen_frame")
@@ -191,7 +195,14 @@ class KPlanesRenderer:
                              "model: pass default_time")
         H, W = cameras.height, cameras.width
         row = tab["distortion"][index] if tab["distortion"] is not None else None
-        if row is not None and any(v != 0.0 for v in row):  # the camera's own row: an all-zero row of a lens table is a pinhole camera
+        lens = row is not None and any(v != 0.0 for v in row)  # the camera's own row: an all-zero row of a lens table is a pinhole camera
+        kind = tab["camera_type"][index] if tab["camera_type"] is not None else CameraType.PERSPECTIVE.value
+        if kind != CameraType.PERSPECTIVE.value:  # a perspective camera of a mixed table takes the entries it always took
+            ra = _lib.RaygenFrameCamArgs()
+            ra.camera_type, ra.has_distortion = kind, int(lens)
+            for k in range(6):
+                ra.distortion[k] = row[k] if lens else 0.0
+        elif lens:
             ra = _lib.RaygenFrameLensArgs()
             for k in range(6):
                 ra.distortion[k] = row[k]
@@ -233,7 +244,7 @@ class KPlanesRenderer:
         are concatenated along the width, single-channel ones repeated to three channels (:117-130).  Returns the list of files written."""
         if format not in ("png", "npy"):
             raise ValueError(f"format={format!r}: 'png' or 'npy' (video encoding is out of scope)")
-        cameras = get_path_from_json(load_camera_path(path))
+        cameras = get_path_from_json(load_camera_path(path), camera_types=ALL_CAMERA_TYPES)
         if cameras.times is None and default_time is None:
             raise ValueError("the camera path has no render_time on every entry and no default_time was given: K-Planes needs a time per frame")
         os.makedirs(output_dir, exist_ok=True)

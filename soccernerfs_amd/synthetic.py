@@ -263,7 +263,10 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
     """uint8 images [M,H,W,3] on `device` for every (camera in cam_ids) x (time), plus per-image camera tables
     (one 'camera' per image, as nerfstudio's Cameras object holds them: c2w/intrinsics repeated per frame + times).
     cams may carry "distortion": OpenCV rows k1 k2 k3 k4 p1 p2, [n_cams,6] or [6] for all cameras.  The dataset is then shot through that lens
-    (ops.generate_rays(distortion_params=...)) and the returned table carries "distortion" [M,6]; without the entry nothing changes."""
+    (ops.generate_rays(distortion_params=...)) and the returned table carries "distortion" [M,6]; without the entry nothing changes.
+    cams may carry "camera_type": an int or CameraType for all cameras, or one per camera [n_cams] (1 perspective, 2 fisheye, 3 equirectangular).
+    The dataset is then shot with cameras of those types (ops.generate_rays(camera_type=...)) and the returned table carries "camera_type"
+    int32 [M]; without the entry nothing changes."""
     from . import ops
 
     H, W = cams["height"], cams["width"]
@@ -274,6 +277,12 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
     if lens is not None:
         lens = torch.as_tensor(lens, dtype=torch.float32).reshape(-1, 6)
         tab["distortion"] = []
+    kinds = cams.get("camera_type")
+    if kinds is not None:
+        kinds = torch.as_tensor(getattr(kinds, "value", kinds), dtype=torch.int32).reshape(-1)
+        if not all(k in ops.CAMERA_TYPES for k in kinds.tolist()):  # checked once here, on the host: the chunks below do not read it back
+            raise ValueError(f"camera_type {kinds.tolist()}: expected values among {ops.CAMERA_TYPES}")
+        tab["camera_type"] = []
     m = 0
     for c in cam_ids:
         for t in times.tolist():
@@ -283,6 +292,8 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             tab["cam_id"].append(c)
             if lens is not None:
                 tab["distortion"].append(lens[c if lens.shape[0] > 1 else 0])
+            if kinds is not None:
+                tab["camera_type"].append(kinds[c if kinds.shape[0] > 1 else 0])
             m += 1
     table = {k: torch.stack(v).to(device).contiguous() for k, v in tab.items() if k not in ("times", "cam_id")}
     table["times"] = torch.tensor(tab["times"], dtype=torch.float32, device=device)
@@ -294,7 +305,7 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             yy, xx = torch.meshgrid(rows, xs, indexing="ij")
             idx = torch.stack([torch.full_like(yy, m), yy, xx], -1).reshape(-1, 3)
             rays = ops.generate_rays(idx, table["fx"], table["fy"], table["cx"], table["cy"], table["c2w"], table["times"],
-                                     distortion_params=table.get("distortion"))
+                                     distortion_params=table.get("distortion"), camera_type=table.get("camera_type"), validate_camera_type=False)
             col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant)
             imgs[m, r0:r0 + rows.numel()] = (col.view(rows.numel(), W, 3) * 255.0 + 0.5).to(torch.uint8)
     return {"images": imgs, **table, "width": W, "height": H}

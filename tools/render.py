@@ -6,7 +6,8 @@
 
 Builds a KPlanesTrainConfig (the k-planes preset unless overridden on the command line -- the checkpoint holds parameters, not the model
 configuration, so the overrides must describe the model that was trained), loads the newest `step-*.ckpt` of --load-dir (or --load-step) with
-KPlanesTrainer.load_checkpoint and writes one `%05d.png` (or `.npy`) per camera of the path into --output-path.  Video files are not
+KPlanesTrainer.load_checkpoint and writes one `%05d.png` (or `.npy`) per camera of the path into --output-path.  The path's "camera_type"
+may be "perspective", "fisheye" or "equirectangular" (a 360-degree frame: fx = W / 2, fy = H, as the viewer exports it).  Video files are not
 written: no encoder is assumed."""
 import argparse
 import ast

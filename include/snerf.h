@@ -36,7 +36,8 @@ typedef void* snerf_stream_t; /* hipStream_t */
  * Revision 2: snerf_raygen_lens, snerf_raygen_frame_lens (rays through the cameras' OpenCV lens distortion).
  * Revision 2's surface also holds snerf_raygen_cam, snerf_raygen_frame_cam and snerf_sample_pixels_sphere (fisheye and equirectangular
  * cameras), added WITHOUT counting a revision: callers and tests pin revision 2.  The binding lists them among the symbols it requires, so a
- * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call. */
+ * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call.
+ * The same holds for snerf_mask_pack and snerf_sample_pixels_masked (pixel draws inside image masks). */
 #define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
@@ -707,6 +708,30 @@ int snerf_sample_pixels_uniform(const float* u, int32_t R, int32_t M, int32_t H,
  * reference evaluates it, with snerf_sample_pixels_uniform's argument list and its fused gather. */
 int snerf_sample_pixels_sphere(const float* u, int32_t R, int32_t M, int32_t H, int32_t W, const uint8_t* images, int64_t* indices,
                                float* target, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface): pixel draws inside image masks.  Replaces PixelSampler.sample_method's masked branch
+ * (NS/data/pixel_samplers.py:69-72: torch.nonzero(mask[..., 0]) over the whole image cache on every step, then a host random.sample).
+ *
+ * snerf_mask_pack packs a byte mask (bool or uint8, any non-zero byte is a valid pixel; flat over [M,H,W], n_pixels in all) into a rank-select
+ * index, once per image-cache refresh.  `mask` points at the `count` bytes of the pixels [first_pixel, first_pixel + count) -- a chunk, so that a
+ * host mask can be streamed through a buffer smaller than itself -- and never more than those bytes are read.  first_pixel % 1024 == 0; count is a
+ * multiple of 1024 unless the range ends at n_pixels.  `bits` and `block_counts` are the WHOLE index; the call writes its range of them:
+ *   bits          uint32 [ceil(n_pixels / 32)]: bit i of word w = pixel 32 w + i (numpy.packbits(bitorder="little") viewed as uint32); the bits
+ *                 past n_pixels in the last word are zero;
+ *   block_counts  int32 [ceil(n_pixels / 1024)]: the set bits of each block of 1024 pixels (32 words; the last block may be partial).
+ * The draw takes the EXCLUSIVE int64 prefix of block_counts, block_prefix [n_blocks + 1] with block_prefix[n_blocks] = the number of valid pixels
+ * (a cumsum at prepare time). */
+int snerf_mask_pack(const uint8_t* mask, int64_t n_pixels, int64_t first_pixel, int64_t count, uint32_t* bits, int32_t* block_counts,
+                    snerf_stream_t stream);
+
+/* The per-step draw (pixel_samplers.py:69-72 and the gather of :111-123): indices[R,3] = torch.nonzero(mask[..., 0])[rank] as int64 (image, row,
+ * col), the valid pixels in row-major order, for rank = floor(v * total / 2^48), v = floor(u0 * 2^24) * 2^24 + floor(u1 * 2^24) from u [R,2]
+ * (each factor clamped to [0, 2^24 - 1], NaN -> 0; two uniforms because a float32 carries 24 bits and a cache holds more pixels than 2^24) and
+ * total = block_prefix[n_blocks], read on the device.  All in integers: exact.  Draws are independent, i.e. WITH replacement, as the unmasked
+ * draw is (the reference's random.sample draws without, and raises when the mask holds fewer pixels than the batch).  n_blocks =
+ * ceil(M H W / 1024).  Fused gather and NULL images as snerf_sample_pixels_uniform.  total == 0 (no valid pixel) draws pixel (0,0,0). */
+int snerf_sample_pixels_masked(const float* u, int32_t R, int32_t M, int32_t H, int32_t W, const uint32_t* bits, const int64_t* block_prefix,
+                               int64_t n_blocks, const uint8_t* images, int64_t* indices, float* target, snerf_stream_t stream);
 
 /* The ray batch in order of a per-image key (image_key[M] in [0, n_keys): the rank of the image's frame time).  A batch is a set (losses are
  * means over it, the per-ray draws are i.i.d.), so its order is free; with equal-time rays adjacent, the gathers of every plane that holds the

@@ -159,7 +159,8 @@ def lib():
         )
     l = C.CDLL(LIB_PATH)
     # entries added to revision 2's surface without a new revision number: a library from before them must fail here, not at the first call
-    missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere") if not hasattr(l, s)]
+    missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere", "snerf_mask_pack", "snerf_sample_pixels_masked")
+               if not hasattr(l, s)]
     if missing:
         raise RuntimeError(f"libsnerf at {LIB_PATH} lacks {', '.join(missing)} (ABI {ABI_VERSION} revision {ABI_REVISION}): rebuild the library")
     l.snerf_last_error.restype = C.c_char_p
@@ -187,6 +188,8 @@ def lib():
     l.snerf_render_mse_bwd.argtypes = [P, P, P, I, P, P, F, I, I, P, P, P, P]
     l.snerf_sample_pixels_uniform.argtypes = [P, I, I, I, I, P, P, P, P]
     l.snerf_sample_pixels_sphere.argtypes = [P, I, I, I, I, P, P, P, P]
+    l.snerf_mask_pack.argtypes = [P, L, L, L, P, P, P]
+    l.snerf_sample_pixels_masked.argtypes = [P, I, I, I, I, P, P, L, P, P, P, P]
     l.snerf_sort_rays_by_key.argtypes = [P, P, I, I, P, I, P, P, P]
     l.snerf_trunc_exp_fwd.argtypes = [P, L, P, P]
     l.snerf_trunc_exp_bwd.argtypes = [P, P, L, P, P]
@@ -269,6 +272,8 @@ EXPORTS = [
     "snerf_adam_step_tv",
     "snerf_sample_pixels_uniform",
     "snerf_sample_pixels_sphere",
+    "snerf_mask_pack",
+    "snerf_sample_pixels_masked",
     "snerf_sort_rays_by_key",
     "snerf_kplanes_scatter_sorted_scales",
     "snerf_raygen",

@@ -8,8 +8,8 @@ all-zero rows (for which the undistortion is the identity), takes the pinhole ke
 camera_type (CameraType, cameras.py:42-58) says how a camera maps its undistorted image coordinates to a direction (cameras.py:663-696):
 PERSPECTIVE (x, y, -1); FISHEYE, the equidistant model, theta = |(x, y)| clipped to pi; EQUIRECTANGULAR, longitude -pi x and colatitude
 pi (0.5 - y), for which the lens row is ignored (:645-647).  An all-perspective table keeps the two entries above, launch for launch; any
-other table -- a mixed one is legal -- takes snerf_raygen_cam, which branches per ray.  The camera optimiser's distortion_params_delta and
-masks are not built."""
+other table -- a mixed one is legal -- takes snerf_raygen_cam, which branches per ray.  The camera optimiser's distortion_params_delta is
+not built.  Image masks belong to the pixel samplers, not to the rays: dataparsers.load_mask_cache, ops.MaskIndex, PixelSampler(mask=...)."""
 import copy
 from enum import Enum
 from typing import Optional, Union

@@ -395,3 +395,23 @@ def load_image_cache(image_filenames: List[Path]) -> torch.Tensor:
             raise NotImplementedError(f"{f}: {im.shape[2]} channels; the image cache holds 8-bit RGB")
         out.append(torch.from_numpy(im))
     return torch.stack(out)
+
+
+def load_mask_cache(mask_filenames: List[Path], scale_factor: float = 1.0) -> torch.Tensor:
+    """get_image_mask_tensor_from_path (NS/data/utils/data_utils.py:25-37) for every file, as InputDataset.get_data loads them
+    (base_dataset.py:99-104): bool [M,H,W,1] on the host, True = a pixel that may be drawn.  Scaled masks are resized to
+    (int(w * s), int(h * s)) with Image.NEAREST; a mask with more than one channel raises ValueError.  load_image_cache's counterpart:
+    what ops.MaskIndex.from_host / PixelSampler's batch["mask"] take."""
+    from PIL import Image
+
+    out = []
+    for f in mask_filenames:
+        pil_mask = Image.open(f)
+        if scale_factor != 1.0:
+            width, height = pil_mask.size
+            pil_mask = pil_mask.resize((int(width * scale_factor), int(height * scale_factor)), resample=Image.NEAREST)
+        mask = torch.from_numpy(np.array(pil_mask)).unsqueeze(-1).bool()
+        if mask.dim() != 3:
+            raise ValueError(f"{f}: the mask image should have 1 channel")
+        out.append(mask)
+    return torch.stack(out)

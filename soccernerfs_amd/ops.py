@@ -898,6 +898,104 @@ def sample_pixels_sphere(u: torch.Tensor, num_images: int, height: int, width: i
     return idx, target
 
 
+MASK_BLOCK = 1024  # pixels per counted block of a MaskIndex (csrc/pixel_mask.hip)
+
+
+def _mask_bytes(mask: torch.Tensor, name: str) -> torch.Tensor:
+    """A bool / uint8 mask as its flat bytes (any non-zero byte is a valid pixel)."""
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"{name}: expected a bool or uint8 mask, got {mask.dtype}")
+    flat = mask.contiguous().reshape(-1)
+    return flat.view(torch.uint8) if flat.dtype == torch.bool else flat
+
+
+def mask_pack(mask_bytes: torch.Tensor, n_pixels: int, first_pixel: int, bits: torch.Tensor, block_counts: torch.Tensor):
+    """snerf_mask_pack: packs the device bytes of the pixels [first_pixel, first_pixel + len(mask_bytes)) of an n_pixels mask into their place in
+    bits (int32 storage of the uint32 words, [ceil(n_pixels / 32)]) and block_counts (int32 [ceil(n_pixels / 1024)])."""
+    if not mask_bytes.is_cuda or mask_bytes.dtype != torch.uint8 or mask_bytes.dim() != 1 or not mask_bytes.is_contiguous():
+        raise RuntimeError("mask_pack: mask_bytes must be a flat contiguous uint8 HIP tensor")
+    for t, n, what in ((bits, -(-n_pixels // 32), "bits"), (block_counts, -(-n_pixels // MASK_BLOCK), "block_counts")):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+            raise RuntimeError(f"mask_pack: {what} must be a contiguous int32 HIP tensor of at least {n} elements")
+    _lib.check(_lib.lib().snerf_mask_pack(_ptr(mask_bytes), n_pixels, first_pixel, mask_bytes.numel(), _ptr(bits), _ptr(block_counts), _stream()),
+               "mask_pack")
+
+
+class MaskIndex:
+    """Rank-select index of an image mask [M,H,W] (True / non-zero = a pixel that may be drawn), resident in place of the byte mask and of the
+    reference's per-step torch.nonzero list (pixel_samplers.py:69-72): `bits` one bit per pixel (int32 storage of uint32 words, little-endian
+    bit order), `block_counts` the valid pixels of every 1024-pixel block, `block_prefix` their exclusive int64 prefix [n_blocks + 1] and
+    `total` = block_prefix[-1], read ONCE here -- the only sync, at prepare time; the draws (sample_pixels_masked) read it on the device."""
+
+    def __init__(self, shape, device):
+        self.shape = tuple(int(s) for s in shape)
+        if len(self.shape) != 3 or min(self.shape) < 1:
+            raise ValueError(f"MaskIndex: the mask must be [M,H,W] or [M,H,W,1] with no empty axis, got {tuple(shape)}")
+        self.n_pixels = self.shape[0] * self.shape[1] * self.shape[2]
+        self.n_blocks = -(-self.n_pixels // MASK_BLOCK)
+        self.bits = torch.empty(-(-self.n_pixels // 32), dtype=torch.int32, device=device)
+        self.block_counts = torch.empty(self.n_blocks, dtype=torch.int32, device=device)
+        self.block_prefix, self.total = None, 0
+
+    @staticmethod
+    def _shape_of(mask: torch.Tensor):
+        return mask.shape[:3] if mask.dim() == 4 and mask.shape[3] == 1 else mask.shape
+
+    def _finish(self):
+        self.block_prefix = torch.zeros(self.n_blocks + 1, dtype=torch.int64, device=self.bits.device)
+        torch.cumsum(self.block_counts, 0, dtype=torch.int64, out=self.block_prefix[1:])
+        self.total = int(self.block_prefix[-1])
+        if self.total == 0:
+            raise ValueError("MaskIndex: the mask holds no valid pixel")
+        return self
+
+    @classmethod
+    def from_mask(cls, mask: torch.Tensor) -> "MaskIndex":
+        """mask: bool / uint8 HIP tensor [M,H,W] or [M,H,W,1]."""
+        if not mask.is_cuda:
+            raise RuntimeError("MaskIndex.from_mask: expected a HIP device tensor (MaskIndex.from_host streams a host mask)")
+        index = cls(cls._shape_of(mask), mask.device)
+        mask_pack(_mask_bytes(mask, "MaskIndex.from_mask"), index.n_pixels, 0, index.bits, index.block_counts)
+        return index._finish()
+
+    @classmethod
+    def from_host(cls, mask_cpu: torch.Tensor, device, chunk_pixels: int = 1 << 26) -> "MaskIndex":
+        """A host mask streamed through the device in chunks of chunk_pixels (a multiple of 1024): only the packed index is ever resident."""
+        if mask_cpu.is_cuda:
+            raise RuntimeError("MaskIndex.from_host: expected a host tensor")
+        if chunk_pixels < MASK_BLOCK or chunk_pixels % MASK_BLOCK:
+            raise ValueError(f"MaskIndex.from_host: chunk_pixels={chunk_pixels} must be a positive multiple of {MASK_BLOCK}")
+        index = cls(cls._shape_of(mask_cpu), device)
+        flat = _mask_bytes(mask_cpu, "MaskIndex.from_host")
+        for first in range(0, index.n_pixels, chunk_pixels):
+            mask_pack(flat[first:first + chunk_pixels].to(device), index.n_pixels, first, index.bits, index.block_counts)
+        return index._finish()
+
+
+def sample_pixels_masked(u: torch.Tensor, index: MaskIndex, num_images: int, height: int, width: int, images: Optional[torch.Tensor] = None):
+    """PixelSampler.sample_method's draw inside a mask (pixel_samplers.py:69-72) from u = rand(R,2): row rank of torch.nonzero(mask[..., 0]) with
+    rank = floor((floor(u0 2^24) 2^24 + floor(u1 2^24)) * total / 2^48); independent draws (with replacement).  The same fused gather and the
+    same returns as sample_pixels_uniform."""
+    u = _f32c(u, "u")
+    if u.dim() != 2 or u.shape[1] != 2:
+        raise RuntimeError(f"sample_pixels_masked: u must be [R,2], got {tuple(u.shape)}")
+    if index.shape != (num_images, height, width):
+        raise ValueError(f"sample_pixels_masked: the mask is {index.shape}, the images are {(num_images, height, width)}")
+    if index.bits.device != u.device:
+        raise RuntimeError("sample_pixels_masked: the mask index and u are on different devices")
+    R = u.shape[0]
+    idx = torch.empty(R, 3, dtype=torch.int64, device=u.device)
+    target = None
+    if images is not None:
+        if not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous() or tuple(images.shape) != (num_images, height, width, 3):
+            raise RuntimeError("sample_pixels_masked: images must be a contiguous uint8 HIP tensor [M,H,W,3]")
+        target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
+    _lib.check(_lib.lib().snerf_sample_pixels_masked(_ptr(u), R, num_images, height, width, _ptr(index.bits), _ptr(index.block_prefix), index.n_blocks,
+                                                     _ptr(images) if images is not None else None, _ptr(idx),
+                                                     _ptr(target) if target is not None else None, _stream()), "sample_pixels_masked")
+    return idx, target
+
+
 def aabb_collide(origins, directions, aabb, near_plane: float = 0.0, training: bool = True):
     """AABBBoxCollider._intersect_with_aabb (scene_colliders.py:59-95) -> (nears [R,1], fars [R,1])."""
     origins, directions = _f32c(origins, "origins"), _f32c(directions, "directions")

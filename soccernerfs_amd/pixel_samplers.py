@@ -132,17 +132,51 @@ class PixelSampler:
     def set_num_rays_per_batch(self, num_rays_per_batch: int):
         self.num_rays_per_batch = num_rays_per_batch
 
+    @staticmethod
+    def mask_index(mask, num_images: int, image_height: int, image_width: int, batch: Optional[Dict] = None) -> ops.MaskIndex:
+        """The packed index of `mask` (a device bool / uint8 tensor [M,H,W,1] or [M,H,W], or an ops.MaskIndex already), checked against the image
+        shape as InputDataset checks its masks (base_dataset.py:102-104).  Built once and kept in the batch as batch["mask_index"], as "ist_cdf" is."""
+        shape = mask.shape if isinstance(mask, ops.MaskIndex) else tuple(ops.MaskIndex._shape_of(mask))
+        if tuple(shape) != (num_images, image_height, image_width):
+            raise ValueError(f"Mask and image have different shapes. Got {tuple(shape)} and {(num_images, image_height, image_width)}")
+        if isinstance(mask, ops.MaskIndex):
+            return mask
+        if batch is not None and batch.get("mask_index") is not None:
+            return PixelSampler.mask_index(batch["mask_index"], num_images, image_height, image_width)
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda):
+            raise NotImplementedError("masked sampling runs on the HIP device only: there is no host draw (move the mask to the device, or build "
+                                      "ops.MaskIndex.from_host(mask, device) and pass it as batch['mask_index'])")
+        index = ops.MaskIndex.from_mask(mask)
+        if batch is not None:
+            batch["mask_index"] = index
+        return index
+
+    @staticmethod
+    def prepare_mask(batch: Dict) -> Dict:
+        """Once per image-cache refresh: batch["mask_index"] from batch["mask"] (otherwise built at the first draw)."""
+        M, H, W, _ = batch["image"].shape
+        PixelSampler.mask_index(batch["mask"], M, H, W, batch=batch)
+        return batch
+
     def sample_method(self, batch_size: int, num_images: int, image_height: int, image_width: int, mask=None, batch=None, device="cuda"):
         if mask is not None:
-            raise NotImplementedError("masked sampling is not used by the soccer datasets")
+            # :69-72 torch.nonzero(mask[..., 0])[a uniform rank], one kernel on the packed index; independent draws (with replacement), where the
+            # reference's random.sample draws without and raises when the mask holds fewer pixels than the batch
+            index = self.mask_index(mask, num_images, image_height, image_width, batch)
+            return ops.sample_pixels_masked(torch.rand((batch_size, 2), device=device), index, num_images, image_height, image_width)[0]
         # :74-77 floor(rand(R,3) * [M,H,W]).long(), one kernel
         return ops.sample_pixels_uniform(torch.rand((batch_size, 3), device=device), num_images, image_height, image_width)[0]
 
     def collate_image_dataset_batch(self, batch: Dict, num_rays_per_batch: int, keep_full_image: bool = False):
-        """:81-128: batch["image"] [M,H,W,3] (uint8 or float), batch["image_idx"] [M]."""
+        """:81-128: batch["image"] [M,H,W,3] (uint8 or float), batch["image_idx"] [M]; with batch["mask"] [M,H,W,1] (or only its packed
+        batch["mask_index"]) the pixels are drawn inside the mask (:96-105)."""
         device = batch["image"].device
         M, H, W, _ = batch["image"].shape
-        indices = self.sample_method(num_rays_per_batch, M, H, W, batch=batch, device=device)
+        mask = batch["mask_index"] if batch.get("mask_index") is not None else batch.get("mask")
+        if mask is not None:
+            indices = self.sample_method(num_rays_per_batch, M, H, W, mask=mask, batch=batch, device=device)
+        else:
+            indices = self.sample_method(num_rays_per_batch, M, H, W, batch=batch, device=device)
         if batch.get("time_key") is not None:
             # optional, not in the reference: the batch in order of the images' frame time (batch["time_key"], batch["n_time_keys"] =
             # ops.image_time_keys(times)).  A batch is a set, so this is free, and it makes every time-plane / temporal-grid gather coherent
@@ -150,10 +184,13 @@ class PixelSampler:
         c, y, x = indices[:, 0], indices[:, 1], indices[:, 2]
         out = {}
         for key, value in batch.items():
-            if key in ("image_idx", "iter_steps", "ist_cdf", "ist_nonempty", "ist_nnz", "time_key", "n_time_keys") or value is None or not isinstance(value, torch.Tensor):
+            if key in ("image_idx", "iter_steps", "ist_cdf", "ist_nonempty", "ist_nnz", "time_key", "n_time_keys", "mask", "mask_index") or value is None \
+                    or not isinstance(value, torch.Tensor):
                 continue
             v = value[c, y, x]
             out[key] = v.float() / 255.0 if v.dtype == torch.uint8 else v
+        if mask is not None:
+            out["mask"] = torch.ones(indices.shape[0], 1, dtype=torch.bool, device=device)  # mask[c, y, x]: True by construction of the draw
         indices = indices.clone()
         indices[:, 0] = batch["image_idx"][c]
         out["indices"] = indices
@@ -168,11 +205,12 @@ class PixelSampler:
 class EquirectangularPixelSampler(PixelSampler):
     """Pixels of equirectangular images drawn uniformly on the sphere (pixel_samplers.py:228-267): the row by inverse-transform sampling of
     f(phi) = sin(phi) / 2, so that the poles are not over-sampled.  What the datamanagers switch to when every training image is
-    equirectangular (NS/data/datamanagers/dynamic_datamanager.py:104-107).  With a mask the reference falls back to the uniform draw."""
+    equirectangular (NS/data/datamanagers/dynamic_datamanager.py:104-107).  With a mask the reference falls back to the uniform draw inside the mask
+    (:248-253), and so does this."""
 
     def sample_method(self, batch_size: int, num_images: int, image_height: int, image_width: int, mask=None, batch=None, device="cuda"):
         if mask is not None:
-            return super().sample_method(batch_size, num_images, image_height, image_width, mask=mask, device=device)
+            return super().sample_method(batch_size, num_images, image_height, image_width, mask=mask, batch=batch, device=device)
         # :259-265 floor((rand, acos(1 - 2 rand) / pi, rand) * [M,H,W]).long(), one kernel
         return ops.sample_pixels_sphere(torch.rand((batch_size, 3), device=device), num_images, image_height, image_width)[0]
 
@@ -180,18 +218,27 @@ class EquirectangularPixelSampler(PixelSampler):
 class DynamicBasedPixelSampler(PixelSampler):
     """IST/ISG importance sampling (pixel_samplers.py:329-426): floor(is_pixel_ratio * R) rays are drawn from the weight maps,
     10 * ceil(num_ist / M) per image from randomly chosen non-empty images -- without replacement inside an image whenever it has enough
-    non-zero pixels, as torch.multinomial is called at :400-402 --, the rest uniformly; active after iters_to_start_ist."""
+    non-zero pixels, as torch.multinomial is called at :400-402 --, the rest uniformly; active after iters_to_start_ist.
+    A mask reaches the uniform draws only (:362, :421): the importance part ignores it, as the reference's does.  mask_ist_weights (not in the
+    reference, off by default) zeroes the weight maps outside the mask when they are prepared, so that no importance draw lands there either."""
 
     def __init__(self, num_rays_per_batch: int, keep_full_image: bool = False, is_pixel_ratio: float = 0.15, iters_to_start_ist: int = 2000,
-                 **kwargs) -> None:
+                 mask_ist_weights: bool = False, **kwargs) -> None:
         super().__init__(num_rays_per_batch, keep_full_image)
-        self.is_pixel_ratio, self.iters_to_start_ist = is_pixel_ratio, iters_to_start_ist
+        self.is_pixel_ratio, self.iters_to_start_ist, self.mask_ist_weights = is_pixel_ratio, iters_to_start_ist, mask_ist_weights
 
     @staticmethod
-    def prepare(batch: Dict) -> Dict:
-        """Once per image-cache refresh: per-image inclusive prefix sums of the maps + the list of non-empty maps."""
+    def prepare(batch: Dict, mask_ist_weights: bool = False) -> Dict:
+        """Once per image-cache refresh: per-image inclusive prefix sums of the maps + the list of non-empty maps.  mask_ist_weights: of the maps
+        with every weight outside batch["mask"] set to zero."""
         w = batch["ist_weights"]
         M = w.shape[0]
+        if mask_ist_weights:
+            if not isinstance(batch.get("mask"), torch.Tensor):
+                raise ValueError("mask_ist_weights needs the byte mask batch['mask'] (the packed batch['mask_index'] alone does not do)")
+            if batch["mask"].numel() != w.numel():
+                raise ValueError(f"Mask and weight maps have different shapes. Got {tuple(batch['mask'].shape)} and {tuple(w.shape)}")
+            w = torch.where(batch["mask"].reshape(w.shape) != 0, w, torch.zeros((), dtype=w.dtype, device=w.device))
         batch["ist_cdf"] = torch.cumsum(w.reshape(M, -1).float(), dim=1).contiguous()
         batch["ist_nonempty"] = (batch["ist_cdf"][:, -1] > 0).nonzero()[:, 0].contiguous()
         batch["ist_nnz"] = (w.reshape(M, -1) > 0).sum(1).to(torch.int32).contiguous()  # len(torch.nonzero(weight_map)) of :400-402
@@ -201,9 +248,9 @@ class DynamicBasedPixelSampler(PixelSampler):
                       device="cuda"):
         assert batch is not None, "Batch information must be provided for DynamicBasedPixelSampler"
         if batch.get("ist_weights") is None or not (batch.get("iter_steps", 0) > self.iters_to_start_ist):
-            return super().sample_method(batch_size, num_images, image_height, image_width, device=device)
+            return super().sample_method(batch_size, num_images, image_height, image_width, mask=mask, batch=batch, device=device)
         if "ist_cdf" not in batch:
-            self.prepare(batch)
+            self.prepare(batch, self.mask_ist_weights)
         num_ist = floor(self.is_pixel_ratio * batch_size)
         per_image = 10 * (-(-num_ist // num_images))  # :369
         nonempty = batch["ist_nonempty"]
@@ -217,5 +264,5 @@ class DynamicBasedPixelSampler(PixelSampler):
             _lib.check(_lib.lib().snerf_ist_sample(ops._ptr(batch["ist_cdf"]), image_height, image_width, ops._ptr(chosen), ops._ptr(batch["ist_nnz"]),
                                                    per_image, ops._ptr(u), n, ops._ptr(idx), ops._stream()), "ist_sample")
             parts.append(idx)
-        parts.append(super().sample_method(batch_size - n, num_images, image_height, image_width, device=device))
+        parts.append(super().sample_method(batch_size - n, num_images, image_height, image_width, mask=mask, batch=batch, device=device))
         return torch.cat(parts, dim=0)

@@ -309,3 +309,27 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant)
             imgs[m, r0:r0 + rows.numel()] = (col.view(rows.numel(), W, 3) * 255.0 + 0.5).to(torch.uint8)
     return {"images": imgs, **table, "width": W, "height": H}
+
+
+def add_broadcast_overlay(data: Dict[str, torch.Tensor], box, colour=(16, 16, 40), stripe_colour=(255, 255, 255), stripe_width: int = 0) -> torch.Tensor:
+    """Paints a broadcast banner (a scoreboard with a running clock: fixed in IMAGE space, not in the scene) into every image of
+    data["images"] (uint8 [M,H,W,3], in place): the box = (y0, y1, x0, x1), rows [y0, y1) and columns [x0, x1), in a constant colour, and
+    inside it a vertical stripe that moves from the left to the right edge with the image's frame time data["times"] in [0, 1] -- the clock.
+    stripe_width 0: a tenth of the box width, at least one column.
+    Returns the mask that goes with such footage (broadcaststyle_dataparser.py:366-373 mask_path): bool [M,H,W,1], False inside the box."""
+    imgs = data["images"]
+    M, H, W = imgs.shape[:3]
+    y0, y1, x0, x1 = (int(v) for v in box)
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"overlay box {tuple(box)} outside the {H} x {W} images")
+    sw = stripe_width if stripe_width > 0 else max(1, (x1 - x0) // 10)
+    sw = min(sw, x1 - x0)
+    imgs[:, y0:y1, x0:x1] = torch.tensor(colour, dtype=torch.uint8, device=imgs.device)
+    start = x0 + torch.floor(data["times"].reshape(-1).float().clamp(0, 1) * (x1 - x0 - sw)).long()  # [M]
+    cols = torch.arange(W, device=imgs.device)
+    stripe = (cols[None, :] >= start[:, None].to(imgs.device)) & (cols[None, :] < start[:, None].to(imgs.device) + sw)  # [M,W]
+    band = imgs[:, y0:y1]
+    band[stripe[:, None, :].expand(M, y1 - y0, W)] = torch.tensor(stripe_colour, dtype=torch.uint8, device=imgs.device)
+    mask = torch.ones(M, H, W, 1, dtype=torch.bool, device=imgs.device)
+    mask[:, y0:y1, x0:x1] = False
+    return mask

@@ -37,7 +37,8 @@ typedef void* snerf_stream_t; /* hipStream_t */
  * Revision 2's surface also holds snerf_raygen_cam, snerf_raygen_frame_cam and snerf_sample_pixels_sphere (fisheye and equirectangular
  * cameras), added WITHOUT counting a revision: callers and tests pin revision 2.  The binding lists them among the symbols it requires, so a
  * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call.
- * The same holds for snerf_mask_pack and snerf_sample_pixels_masked (pixel draws inside image masks). */
+ * The same holds for snerf_mask_pack and snerf_sample_pixels_masked (pixel draws inside image masks), and for snerf_kplanes_gather_bwd_coords,
+ * snerf_pose_apply and snerf_raygen_pose_bwd (the camera optimiser: coordinate gradients of the plane gather down to SO3xR3 pose deltas). */
 #define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
@@ -90,12 +91,28 @@ typedef struct {
 int snerf_kplanes_gather_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords,
                              int64_t N, float* out, snerf_stream_t stream);
 
-/* Backward of the above w.r.t. the planes (coordinates carry no gradient on this path: camera
- * optimiser off).  ACCUMULATES (atomic fp32 adds) into grad_planes, which has the
+/* Backward of the above w.r.t. the planes (the coordinates' gradient, which the camera optimiser needs,
+ * is snerf_kplanes_gather_bwd_coords below).  ACCUMULATES (atomic fp32 adds) into grad_planes, which has the
  * layout of `planes`; the caller zeroes it when needed.  Replaces ATen grid_sampler_2d_backward x 6
  * per scale + the product rule. */
 int snerf_kplanes_gather_bwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords,
                              int64_t N, const float* grad_out, float* grad_planes, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface, see SNERF_ABI_REVISION): backward of snerf_kplanes_gather_fwd w.r.t. the sample COORDINATES, and
+ * its reduction to the ray.  Replaces what autograd does in the reference when the camera optimiser is on (NS/cameras/camera_optimizers.py:67-133):
+ * ATen grid_sampler_2d_backward's grid gradient x 6 planes per scale + the product rule of interpolate_kplanes (NS/fields/kplanes_field.py:77-126),
+ * then SceneBox.get_normalized_positions (NS/data/scene_box.py:55-65) and Frustums.get_positions (NS/cameras/rays.py:54) back to the ray.
+ * grad_out is snerf_kplanes_gather_bwd's.  Either output group may be NULL:
+ *   grad_pts [N, n_coords]  WRITTEN: d / d(the [-1,1] coordinate the planes see), time column included; coords mode 0 and mode 1.
+ *   grad_origins, grad_dirs [R,3]  ACCUMULATED (+=), mode 1 only: g_o += k sum_s g_p(s), g_d += k sum_s tmid(s) g_p(s) with
+ *                           tmid = (e[s] + e[s+1]) / 2 and k = (rescale ? 2 : 1) / (aabb_max - aabb_min) per axis.  Time carries no gradient
+ *                           to the ray.  The sum over a ray's samples runs in a fixed order, without atomics: two runs give the same bits.
+ * Semantics are ATen's for bilinear, align_corners=True, border padding: along an axis the slope is (W - 1) / 2 times the difference of the two
+ * texel columns weighted by the other axis; zero where the unnormalised coordinate is clipped (<= 0 or >= W - 1), so also for a resolution of 1.
+ * DELIBERATE DEVIATION: the bin edges e[] are constants.  The reference's autograd also differentiates the collider's nears / fars (and with
+ * them every bin edge) with respect to the ray; here the gradient is that of moving the samples rigidly with the ray. */
+int snerf_kplanes_gather_bwd_coords(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
+                                    const float* grad_out, float* grad_pts, float* grad_origins, float* grad_dirs, snerf_stream_t stream);
 
 /* Deterministic accumulation.  Float atomics make a sum depend on the order in which wavefronts arrive (torch's own
  * grid_sampler_2d_backward has the same property on GPUs).  The _fx entry points accumulate into 64-bit fixed-point cells instead
@@ -696,6 +713,44 @@ typedef struct {
   int32_t has_distortion;
 } snerf_raygen_frame_cam_args;
 int snerf_raygen_frame_cam(const snerf_raygen_frame_cam_args* args, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface): the camera optimiser, mode SO3xR3 (NS/cameras/camera_optimizers.py:67-133,
+ * NS/cameras/lie_groups.py:23-58, NS/cameras/cameras.py:707-708, NS/utils/poses.py:53-67).
+ *
+ * snerf_pose_apply: c2w_adj[m] = multiply(c2w[m], exp_map_SO3xR3(pose_adjustment[group[m]])), i.e. R' = R E, t' = t + R tau, for the whole
+ * table [M,3,4].  pose_adjustment [G,6] holds the translation first, then the so(3) vector; group is int32 [M] with values in [0, G), or NULL
+ * for one row per camera (G == M, the reference's behaviour).  The arithmetic is the reference's in float32, clamp(|w|^2, 1e-4) included.  An
+ * all-zero row passes its camera through bit for bit.  The raygen entry points then run on c2w_adj unchanged: that is the whole forward.
+ *
+ * snerf_raygen_pose_bwd: grad_pose_fx[group[c]] += d(sum_r g_origins[r] . o_r + g_dirs[r] . d_r) / d pose_adjustment over the batch's rays,
+ * through the normalisation of the world direction, the composition and the exp map.  The camera-space direction is recomputed with the
+ * forward's code (all camera types, the lens) and is a constant of the pose; so are the pixel area and directions_norm's gradient (none).
+ * While |w|^2 < 1e-4 the clamp makes fac1 and fac2 constants, as autograd sees them; from 1e-4 on they carry gradient.  c2w is the
+ * UNADJUSTED table.  grad_pose_fx is int64 [G,6] in the 2^50 fixed-point cells of snerf_fx_to_float, which turns them into floats: the result
+ * does not depend on the order in which the rays arrive.  Rays whose camera or group index lies outside the tables add nothing.  A non-finite
+ * contribution adds nothing to the cells (as in every fixed-point accumulation here) and raises nonfinite_flag, so that snerf_adam_prepare
+ * skips the pose group's step as GradScaler would.
+ * DELIBERATE DEVIATION (with snerf_kplanes_gather_bwd_coords): nears / fars and the bin edges carry no gradient. */
+int snerf_pose_apply(const float* c2w, const float* pose_adjustment, const int32_t* group, int32_t M, int32_t G, float* c2w_adj,
+                     snerf_stream_t stream);
+typedef struct {
+  const int64_t* indices;     /* [R,3] (camera, row, col) */
+  const float* fx; const float* fy; const float* cx; const float* cy; /* [M] */
+  const float* c2w;           /* [M,3,4], unadjusted */
+  const float* distortion;    /* [M,6] (stride 6), [6] (stride 0) or NULL (no lens) */
+  const int32_t* camera_type; /* [M] (stride 1), [1] (stride 0) or NULL (all perspective) */
+  const float* pose_adjustment; /* [G,6] */
+  const int32_t* group;       /* [M] or NULL (G == M) */
+  const float* g_origins;     /* [R,3] */
+  const float* g_dirs;        /* [R,3] */
+  int64_t* grad_pose_fx;      /* [G,6] fixed-point cells, accumulated */
+  int32_t* nonfinite_flag;    /* NULL, or the pose group's snerf_adam_dyn: 1 is stored when a ray's pose gradient is not finite */
+  int32_t distortion_stride;
+  int32_t camera_type_stride;
+  int32_t M, G, R;
+  int32_t _pad;
+} snerf_raygen_pose_bwd_args;
+int snerf_raygen_pose_bwd(const snerf_raygen_pose_bwd_args* args, snerf_stream_t stream);
 
 /* PixelSampler.sample_method (NS/data/pixel_samplers.py:74-77): indices[R,3] = floor(u[R,3] * (M,H,W)) as int64 (image, row, col), fused
  * with collate_image_dataset_batch's gather (:111-123): target[R,3] = images[c,y,x,:] / 255 for a resident uint8 image cache

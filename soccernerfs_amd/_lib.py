@@ -122,6 +122,15 @@ class RaygenFrameCamArgs(C.Structure):
     _fields_ = RaygenFrameLensArgs._fields_ + [("camera_type", C.c_int32), ("has_distortion", C.c_int32)]
 
 
+class RaygenPoseBwdArgs(C.Structure):
+    """snerf_raygen_pose_bwd_args (added to ABI 16 revision 2, csrc/raygen.hip): the batch, the camera table, the pose rows and the ray gradients."""
+    _fields_ = [("indices", C.c_void_p), ("fx", C.c_void_p), ("fy", C.c_void_p), ("cx", C.c_void_p), ("cy", C.c_void_p), ("c2w", C.c_void_p),
+                ("distortion", C.c_void_p), ("camera_type", C.c_void_p), ("pose_adjustment", C.c_void_p), ("group", C.c_void_p),
+                ("g_origins", C.c_void_p), ("g_dirs", C.c_void_p), ("grad_pose_fx", C.c_void_p), ("nonfinite_flag", C.c_void_p),
+                ("distortion_stride", C.c_int32), ("camera_type_stride", C.c_int32), ("M", C.c_int32), ("G", C.c_int32), ("R", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 class TgridDesc(C.Structure):
     _fields_ = [("D", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("grid_C", C.c_int32), ("H", C.c_int32), ("gridtype", C.c_int32),
                 ("align_corners", C.c_int32), ("S", C.c_float), ("offsets", C.c_int32 * 33)]
@@ -159,7 +168,8 @@ def lib():
         )
     l = C.CDLL(LIB_PATH)
     # entries added to revision 2's surface without a new revision number: a library from before them must fail here, not at the first call
-    missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere", "snerf_mask_pack", "snerf_sample_pixels_masked")
+    missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere", "snerf_mask_pack", "snerf_sample_pixels_masked",
+                                "snerf_kplanes_gather_bwd_coords", "snerf_pose_apply", "snerf_raygen_pose_bwd")
                if not hasattr(l, s)]
     if missing:
         raise RuntimeError(f"libsnerf at {LIB_PATH} lacks {', '.join(missing)} (ABI {ABI_VERSION} revision {ABI_REVISION}): rebuild the library")
@@ -217,6 +227,9 @@ def lib():
     l.snerf_raygen_frame_lens.argtypes = [P, P]
     l.snerf_raygen_cam.argtypes = [P, P]
     l.snerf_raygen_frame_cam.argtypes = [P, P]
+    l.snerf_kplanes_gather_bwd_coords.argtypes = [P, P, P, L, P, P, P, P, P]
+    l.snerf_pose_apply.argtypes = [P, P, P, I, I, P, P]
+    l.snerf_raygen_pose_bwd.argtypes = [P, P]
     if l.snerf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
     revision = l.snerf_abi_revision() if hasattr(l, "snerf_abi_revision") else 0  # a library from before revisions were counted
@@ -240,6 +253,9 @@ EXPORTS = [
     "snerf_target_arch",
     "snerf_kplanes_gather_fwd",
     "snerf_kplanes_gather_bwd",
+    "snerf_kplanes_gather_bwd_coords",
+    "snerf_pose_apply",
+    "snerf_raygen_pose_bwd",
     "snerf_spaced_bins",
     "snerf_weights_fwd",
     "snerf_weights_bwd",

@@ -8,8 +8,8 @@ all-zero rows (for which the undistortion is the identity), takes the pinhole ke
 camera_type (CameraType, cameras.py:42-58) says how a camera maps its undistorted image coordinates to a direction (cameras.py:663-696):
 PERSPECTIVE (x, y, -1); FISHEYE, the equidistant model, theta = |(x, y)| clipped to pi; EQUIRECTANGULAR, longitude -pi x and colatitude
 pi (0.5 - y), for which the lens row is ignored (:645-647).  An all-perspective table keeps the two entries above, launch for launch; any
-other table -- a mixed one is legal -- takes snerf_raygen_cam, which branches per ray.  The camera optimiser's distortion_params_delta is
-not built.  Image masks belong to the pixel samplers, not to the rays: dataparsers.load_mask_cache, ops.MaskIndex, PixelSampler(mask=...)."""
+other table -- a mixed one is legal -- takes snerf_raygen_cam, which branches per ray.  RayGenerator(cameras, pose_optimizer) composes a
+camera_optimizers.CameraOptimizer's SO3xR3 adjustments into the table first; the camera optimiser's distortion_params_delta is not built.  Image masks belong to the pixel samplers, not to the rays: dataparsers.load_mask_cache, ops.MaskIndex, PixelSampler(mask=...)."""
 import copy
 from enum import Enum
 from typing import Optional, Union
@@ -132,13 +132,19 @@ class Cameras:
 
 
 class RayGenerator(nn.Module):
-    """ray_generators.py:27-59 (camera optimiser 'off')."""
+    """ray_generators.py:27-59.  pose_optimizer: a camera_optimizers.CameraOptimizer whose adjustments are composed into the whole table
+    before the rays are formed (one snerf_pose_apply launch per call; cameras.py:707-708); None, or one with mode "off", issues the
+    launches this class always issued."""
 
     def __init__(self, cameras: Cameras, pose_optimizer=None) -> None:
         super().__init__()
         self.cameras = cameras
+        self.pose_optimizer = pose_optimizer
 
     def forward(self, ray_indices: torch.Tensor) -> RayBundle:
         idx = ray_indices.long()
         coords = idx[:, 1:3].float() + 0.5
-        return self.cameras.generate_rays(camera_indices=idx[:, 0:1], coords=coords)
+        cameras = self.cameras
+        if self.pose_optimizer is not None and self.pose_optimizer.config.mode != "off":
+            cameras = self.pose_optimizer.adjusted(cameras)
+        return cameras.generate_rays(camera_indices=idx[:, 0:1], coords=coords)

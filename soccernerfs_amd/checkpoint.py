@@ -186,11 +186,15 @@ def checkpoint_path(checkpoint_dir: str, step: int) -> str:
 
 
 def save_checkpoint(checkpoint_dir: str, step: int, model: nn.Module, optimizers: Optional[Dict[str, Dict]] = None,
-                    save_only_latest_checkpoint: bool = True) -> str:
-    """trainer.py:353-380."""
+                    save_only_latest_checkpoint: bool = True, extra_pipeline: Optional[Dict[str, torch.Tensor]] = None) -> str:
+    """trainer.py:353-380.  extra_pipeline: pipeline entries that do not belong to the model (the camera optimiser's
+    `datamanager.train_camera_optimizer.pose_adjustment`, base_datamanager.py:444-449); None or empty = the file as it always was."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = checkpoint_path(checkpoint_dir, step)
-    torch.save({"step": step, "pipeline": reference_state_dict(model), "optimizers": optimizers or {}, "scalers": {}}, path)
+    pipeline = reference_state_dict(model)
+    for k, t in (extra_pipeline or {}).items():
+        pipeline[k] = t.detach().cpu().contiguous()
+    torch.save({"step": step, "pipeline": pipeline, "optimizers": optimizers or {}, "scalers": {}}, path)
     if save_only_latest_checkpoint:
         for f in os.listdir(checkpoint_dir):
             if f.endswith(".ckpt") and os.path.join(checkpoint_dir, f) != path:
@@ -198,9 +202,10 @@ def save_checkpoint(checkpoint_dir: str, step: int, model: nn.Module, optimizers
     return path
 
 
-def load_checkpoint(load_dir: str, model: nn.Module, load_step: Optional[int] = None, strict: bool = True):
+def load_checkpoint(load_dir: str, model: nn.Module, load_step: Optional[int] = None, strict: bool = True, camera_optimizer=None):
     """trainer.py:331-351: the latest `step-*.ckpt` of load_dir unless load_step is given.  -> (start step = saved step + 1, optimiser
-    moments per parameter as import_optimizer_states returns them)."""
+    moments per parameter as import_optimizer_states returns them).  camera_optimizer: a camera_optimizers.CameraOptimizer that takes its
+    pose adjustments and Adam state from the file (zeros when the file was written without one)."""
     if load_step is None:
         steps = sorted(int(f[f.find("-") + 1: f.find(".")]) for f in os.listdir(load_dir) if f.startswith("step-") and f.endswith(".ckpt"))
         if not steps:
@@ -211,4 +216,6 @@ def load_checkpoint(load_dir: str, model: nn.Module, load_step: Optional[int] = 
         raise FileNotFoundError(f"Checkpoint {path} does not exist")
     loaded = torch.load(path, map_location="cpu", weights_only=False)
     load_reference_state_dict(model, loaded["pipeline"], strict=strict)
+    if camera_optimizer is not None:
+        camera_optimizer.load_checkpoint_entries(loaded["pipeline"], loaded.get("optimizers", {}))
     return loaded["step"] + 1, import_optimizer_states(model, loaded.get("optimizers", {}))

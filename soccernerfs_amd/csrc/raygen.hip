@@ -1,11 +1,15 @@
-// Ray generation (pinhole, through the OpenCV lens distortion, or by camera type: perspective / fisheye / equirectangular; camera optimiser
-// off) fused with the AABB collider.
+// Ray generation (pinhole, through the OpenCV lens distortion, or by camera type: perspective / fisheye / equirectangular) fused with the AABB
+// collider, and the camera optimiser's two kernels around it: the pose rows composed into the camera table before the rays are formed, and the
+// ray gradients taken back to the pose rows.
 //
 // Reference: RayGenerator.forward (NS/model_components/ray_generators.py:41-59) ->
 // Cameras._generate_rays_from_coords (NS/cameras/cameras.py:505-741; the perspective slice :596-633,:663-670,
 // :704-741 -- ~40 small ATen kernels incl. boolean-mask scatters) and AABBBoxCollider._intersect_with_aabb
 // (NS/model_components/scene_colliders.py:59-95).  One lane per ray; the per-camera table (fx,fy,cx,cy,c2w,time)
-// is a few KB and stays in L1/L2.
+// is a few KB and stays in L1/L2.  The raygen kernels themselves know nothing of the camera optimiser: snerf_pose_apply
+// (CameraOptimizer.forward + cameras.py:707-708, NS/cameras/lie_groups.py:23-58; one lane per camera) writes the adjusted table they read,
+// and snerf_raygen_pose_bwd (what autograd does from the rays back to pose_adjustment; one lane per ray, fixed-point cells) is their backward
+// with respect to the pose rows.
 #include "raygen_common.hpp"
 
 #pragma clang fp contract(off)
@@ -178,6 +182,136 @@ __global__ void aabb_kernel(const float* __restrict__ o, const float* __restrict
   nears[r] = tn; fars[r] = tf;
 }
 
+// CameraOptimizer.forward + the composition of cameras.py:707-708 for the whole table: one lane per camera.  group: int32 [M] (the row of
+// pose_adjustment each camera reads) or null (row m).  An all-zero row copies the camera through: the composition would give the same values
+// (E is the identity exactly) but turn a -0.0 of the table into +0.0, and a zero-initialised optimiser must leave the rays bit-identical.
+__global__ void pose_apply_kernel(const float* __restrict__ c2w, const float* __restrict__ adj, const int32_t* __restrict__ group, int M, int G,
+                                  float* __restrict__ out) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const int g = group ? group[m] : m;
+  float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  bool zero = true;
+  if (g >= 0 && g < G) {  // a row outside the table is the identity (the binding refuses such a table)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { a[i] = adj[(int64_t)g * 6 + i]; zero = zero && a[i] == 0.f; }
+  }
+  float mm[12], o[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) mm[i] = c2w[(int64_t)m * 12 + i];
+  if (zero) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) o[i] = mm[i];
+  } else {
+    const PoseExp e = pose_exp_map(a);
+    pose_compose(mm, e.E, a, o);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) out[(int64_t)m * 12 + i] = o[i];
+}
+
+// d(sum g_o . o + g_d . d) / d pose_adjustment, one lane per ray: the camera-space direction v is recomputed (a constant of the pose), then
+//   d = w / |w|, w = R E v        ->  g_w = (g_d - d (d . g_d)) / |w|,  g_E = (R^T g_w) v^T
+//   o = t + R tau                 ->  g_tau = R^T g_o
+//   E = I + fac1 K + fac2 K^2     ->  g_K = fac1 g_E + fac2 (g_E K^T + K^T g_E),  g_fac1 = <g_E, K>,  g_fac2 = <g_E, K^2>
+// fac1 and fac2 are constants while |w|^2 < 1e-4 (torch.clamp passes no gradient below its bound), as autograd sees them; from the bound on they
+// carry gradient through theta.  Rows are accumulated in 2^50-scaled 64-bit cells: any arrival order gives the same bits.
+struct PoseBwdArgs {
+  const int64_t* indices;
+  const float* fx; const float* fy; const float* cx; const float* cy;
+  const float* c2w;
+  const float* distortion; int distortion_stride;
+  const int32_t* camera_type; int camera_type_stride;
+  const float* adj; const int32_t* group;
+  int M, G, R;
+  const float* g_origins; const float* g_dirs;
+  long long* grad_pose_fx;
+  int32_t* nonfinite_flag;
+};
+
+__global__ void raygen_pose_bwd_kernel(PoseBwdArgs a) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.R) return;
+  const int64_t c = a.indices[(int64_t)r * 3], yi = a.indices[(int64_t)r * 3 + 1], xi = a.indices[(int64_t)r * 3 + 2];
+  if (c < 0 || c >= a.M) return;
+  const int g = a.group ? a.group[c] : (int)c;
+  if (g < 0 || g >= a.G) return;
+  const int type = a.camera_type ? a.camera_type[c * a.camera_type_stride] : CAMERA_PERSPECTIVE;
+  const bool lens = a.distortion != nullptr;
+  float k[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) k[i] = lens ? a.distortion[c * a.distortion_stride + i] : 0.f;
+  float v[3];
+  pixel_camera_direction(yi, xi, a.fx[c], a.fy[c], a.cx[c], a.cy[c], type, lens, k, v);
+  float adj[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) adj[i] = a.adj[(int64_t)g * 6 + i];
+  const PoseExp e = pose_exp_map(adj);
+  const float* m = a.c2w + c * 12;
+  float Rm[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rm[i * 3 + j] = m[i * 4 + j];
+  // forward: w = R (E v), d = w / max(|w|, 4 eps)
+  float ev[3], w[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ev[i] = e.E[i * 3] * v[0] + e.E[i * 3 + 1] * v[1] + e.E[i * 3 + 2] * v[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = Rm[i * 3] * ev[0] + Rm[i * 3 + 1] * ev[1] + Rm[i * 3 + 2] * ev[2];
+  const float nraw = sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  const float n = fmaxf(nraw, 8.8817841970012523e-16f);
+  const float d[3] = {w[0] / n, w[1] / n, w[2] / n};
+  float go[3], gd[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { go[i] = a.g_origins[(int64_t)r * 3 + i]; gd[i] = a.g_dirs[(int64_t)r * 3 + i]; }
+  const float dg = d[0] * gd[0] + d[1] * gd[1] + d[2] * gd[2];
+  float gw[3], u[3], gtau[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) gw[i] = (gd[i] - (nraw > 8.8817841970012523e-16f ? d[i] * dg : 0.f)) / n;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    u[j] = Rm[j] * gw[0] + Rm[3 + j] * gw[1] + Rm[6 + j] * gw[2];     // R^T g_w
+    gtau[j] = Rm[j] * go[0] + Rm[3 + j] * go[1] + Rm[6 + j] * go[2];  // R^T g_o
+  }
+  float gE[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gE[i * 3 + j] = u[i] * v[j];
+  float gK[9];
+  float gf1 = 0.f, gf2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      float t = 0.f;  // (g_E K^T + K^T g_E)[i][j]
+#pragma unroll
+      for (int l = 0; l < 3; ++l) t += gE[i * 3 + l] * e.K[j * 3 + l] + e.K[l * 3 + i] * gE[l * 3 + j];
+      gK[i * 3 + j] = e.fac1 * gE[i * 3 + j] + e.fac2 * t;
+      gf1 += gE[i * 3 + j] * e.K[i * 3 + j];
+      gf2 += gE[i * 3 + j] * e.K2[i * 3 + j];
+    }
+  float gwv[3] = {gK[7] - gK[5], gK[2] - gK[6], gK[3] - gK[1]};
+  if (e.nrms >= 1e-4f) {  // above the clamp: fac1 = sin(th) / th, fac2 = (1 - cos(th)) / th^2, th = |w|
+    const float th = sqrtf(e.nrms), sn = sinf(th), cs = cosf(th);
+    const float df1 = (th * cs - sn) / (th * th);
+    const float df2 = (th * sn - 2.f * (1.f - cs)) / (th * th * th);
+    const float gth = (gf1 * df1 + gf2 * df2) / th;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) gwv[i] += gth * adj[3 + i];
+  }
+  if (a.nonfinite_flag) {
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) finite = finite && fabsf(gtau[i]) <= 3.402823466e+38f && fabsf(gwv[i]) <= 3.402823466e+38f;
+    if (!finite) *a.nonfinite_flag = 1;
+  }
+  long long* row = a.grad_pose_fx + (int64_t)g * 6;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { fx_atomic_add(row + i, gtau[i]); fx_atomic_add(row + 3 + i, gwv[i]); }
+}
+
 }  // namespace snerf
 
 using namespace snerf;
@@ -290,5 +424,39 @@ extern "C" int snerf_aabb_collide(const float* origins, const float* dirs, int32
   hipLaunchKernelGGL(aabb_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, (hipStream_t)stream, origins, dirs, R, near_plane, training, nullptr, nears,
                      fars, aabb6[0], aabb6[1], aabb6[2], aabb6[3], aabb6[4], aabb6[5]);
   SNERF_LAUNCH_CHECK("aabb_collide");
+  return 0;
+}
+
+extern "C" int snerf_pose_apply(const float* c2w, const float* pose_adjustment, const int32_t* group, int32_t M, int32_t G, float* c2w_adj,
+                                snerf_stream_t stream) {
+  SNERF_REQUIRE(M >= 0 && G >= 0, "pose_apply: M=%d G=%d", M, G);
+  SNERF_REQUIRE(group || G == M, "pose_apply: no group table, so G=%d must equal M=%d", G, M);
+  if (M == 0) return 0;
+  SNERF_REQUIRE(c2w && pose_adjustment && c2w_adj, "pose_apply: null buffer");
+  hipLaunchKernelGGL(pose_apply_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, (hipStream_t)stream, c2w, pose_adjustment, group, M, G, c2w_adj);
+  SNERF_LAUNCH_CHECK("pose_apply");
+  return 0;
+}
+
+extern "C" int snerf_raygen_pose_bwd(const snerf_raygen_pose_bwd_args* p, snerf_stream_t stream) {
+  SNERF_REQUIRE(p, "raygen_pose_bwd: null args");
+  SNERF_REQUIRE(p->R >= 0 && p->M >= 1 && p->G >= 1, "raygen_pose_bwd: R=%d M=%d G=%d", p->R, p->M, p->G);
+  SNERF_REQUIRE(p->group || p->G == p->M, "raygen_pose_bwd: no group table, so G=%d must equal M=%d", p->G, p->M);
+  SNERF_REQUIRE(p->distortion_stride == 0 || p->distortion_stride == 6, "raygen_pose_bwd: distortion_stride=%d (0: one shared row, 6: a [M,6] table)",
+                p->distortion_stride);
+  SNERF_REQUIRE(p->camera_type_stride == 0 || p->camera_type_stride == 1, "raygen_pose_bwd: camera_type_stride=%d (0: one shared value, 1: an [M] table)",
+                p->camera_type_stride);
+  if (p->R == 0) return 0;
+  SNERF_REQUIRE(p->indices && p->fx && p->fy && p->cx && p->cy && p->c2w && p->pose_adjustment, "raygen_pose_bwd: null camera/index/pose buffer");
+  SNERF_REQUIRE(p->g_origins && p->g_dirs && p->grad_pose_fx, "raygen_pose_bwd: null gradient buffer");
+  PoseBwdArgs a;
+  a.indices = p->indices; a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy; a.c2w = p->c2w;
+  a.distortion = p->distortion; a.distortion_stride = p->distortion_stride;
+  a.camera_type = p->camera_type; a.camera_type_stride = p->camera_type_stride;
+  a.adj = p->pose_adjustment; a.group = p->group; a.M = p->M; a.G = p->G; a.R = p->R;
+  a.g_origins = p->g_origins; a.g_dirs = p->g_dirs; a.grad_pose_fx = reinterpret_cast<long long*>(p->grad_pose_fx);
+  a.nonfinite_flag = p->nonfinite_flag;
+  hipLaunchKernelGGL(raygen_pose_bwd_kernel, dim3(ceil_div(p->R, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  SNERF_LAUNCH_CHECK("raygen_pose_bwd");
   return 0;
 }

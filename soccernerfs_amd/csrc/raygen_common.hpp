@@ -156,6 +156,55 @@ __device__ __forceinline__ PixelRay pixel_ray_cam(int64_t yi, int64_t xi, float 
   return p;
 }
 
+// The camera-space direction of a pixel's CENTRE: the first of pixel_ray_cam's three coordinate pairs, through the same statements (the
+// pair, undistort_pair, camera_direction).  It does not depend on the camera-to-world matrix: the pose backward recomputes it as a constant.
+__device__ __forceinline__ void pixel_camera_direction(int64_t yi, int64_t xi, float fx, float fy, float cx, float cy, int type, bool lens,
+                                                       const float k[6], float v[3]) {
+#pragma clang fp contract(off)
+  const float y = (float)yi + 0.5f, x = (float)xi + 0.5f;
+  float c0 = (x - cx) / fx, c1 = -(y - cy) / fy;
+  if (lens && type != CAMERA_EQUIRECTANGULAR) undistort_pair(c0, c1, k, c0, c1);
+  camera_direction(type, c0, c1, v);
+}
+
+// exp_map_SO3xR3 (NS/cameras/lie_groups.py:23-58) of one tangent vector a = (translation, so(3) vector): E = I + fac1 K + fac2 K^2 with
+// K = skew(w), theta = sqrt(clamp(|w|^2, 1e-4)), fac1 = (1 / theta) sin(theta), fac2 = (1 / theta)(1 / theta)(1 - cos(theta)); the
+// translation is a[0..3) as it stands.  K2 = K K is returned for the backward.  Every product rounded, in the reference's order.
+struct PoseExp {
+  float E[9], K[9], K2[9], fac1, fac2, nrms;
+};
+__device__ __forceinline__ PoseExp pose_exp_map(const float a[6]) {
+#pragma clang fp contract(off)
+  PoseExp e;
+  const float wx = a[3], wy = a[4], wz = a[5];
+  e.nrms = (wx * wx + wy * wy) + wz * wz;
+  const float ang = sqrtf(fmaxf(e.nrms, 1e-4f));
+  const float inv = 1.0f / ang;
+  e.fac1 = inv * sinf(ang);
+  e.fac2 = (inv * inv) * (1.0f - cosf(ang));
+  const float K[9] = {0.f, -wz, wy, wz, 0.f, -wx, -wy, wx, 0.f};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) e.K[i] = K[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) e.K2[i * 3 + j] = (K[i * 3] * K[j] + K[i * 3 + 1] * K[3 + j]) + K[i * 3 + 2] * K[6 + j];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) e.E[i] = (e.fac1 * e.K[i] + e.fac2 * e.K2[i]) + ((i % 4 == 0) ? 1.f : 0.f);
+  return e;
+}
+
+// pose_utils.multiply(c2w, [E | tau]) (NS/utils/poses.py:53-67, as NS/cameras/cameras.py:707-708 composes it): R' = R E, t' = t + R tau
+__device__ __forceinline__ void pose_compose(const float* m /*3x4*/, const float E[9], const float tau[3], float out[12]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[i * 4 + j] = (m[i * 4] * E[j] + m[i * 4 + 1] * E[3 + j]) + m[i * 4 + 2] * E[6 + j];
+    out[i * 4 + 3] = m[i * 4 + 3] + ((m[i * 4] * tau[0] + m[i * 4 + 1] * tau[1]) + m[i * 4 + 2] * tau[2]);
+  }
+}
+
 // AABBBoxCollider: near_plane applies in training only
 __device__ __forceinline__ void aabb_interval(const float o[3], const float d[3], const float mn[3], const float mx[3], float near_plane, int training,
                                               float& tn_out, float& tf_out) {

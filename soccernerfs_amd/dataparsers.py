@@ -415,3 +415,16 @@ def load_mask_cache(mask_filenames: List[Path], scale_factor: float = 1.0) -> to
             raise ValueError(f"{f}: the mask image should have 1 channel")
         out.append(mask)
     return torch.stack(out)
+
+
+def camera_pose_groups(cameras_or_ids) -> "torch.Tensor":
+    """LongTensor [M]: for each image of a camera table the index of its PHYSICAL camera (the rank of its camera id among the table's distinct
+    ids) -- the `groups` of camera_optimizers.CameraOptimizer, with which the frames of one static camera share one pose adjustment.
+    Takes a Cameras built by these parsers (its `ids`) or the ids themselves."""
+    import torch
+
+    ids = getattr(cameras_or_ids, "ids", cameras_or_ids)
+    if ids is None:
+        raise ValueError("camera_pose_groups: the camera table carries no camera ids")
+    _, inv = torch.unique(torch.as_tensor(ids).reshape(-1).cpu(), sorted=True, return_inverse=True)
+    return inv.to(torch.int64)

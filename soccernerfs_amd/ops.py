@@ -65,7 +65,8 @@ class _KPlanesGather(torch.autograd.Function):
     autograd off, so everything up to the last space plane -- XY, XZ, XT, YZ -- is cut off; only YT and ZT receive a gradient.  Reproduced)."""
 
     @staticmethod
-    def forward(ctx, planes, ps: PlaneSet, coords_keepalive, coords: _lib.Coords, N: int, freeze: int = 0):
+    def forward(ctx, planes, ps: PlaneSet, coords_keepalive, coords: _lib.Coords, N: int, freeze: int = 0, pts=None):
+        """pts: the points tensor itself (coords mode 0) when it asks for a gradient -- the camera optimiser's path; None otherwise."""
         out = torch.empty(N, ps.out_dim, dtype=torch.float32, device=planes.device)
         desc = ps.space_desc() if freeze & 1 else ps.desc()
         _lib.check(_lib.lib().snerf_kplanes_gather_fwd(C.byref(desc), _ptr(planes), C.byref(coords), C.c_int64(N), _ptr(out), _stream()),
@@ -78,16 +79,46 @@ class _KPlanesGather(torch.autograd.Function):
     def backward(ctx, gout):
         (planes,) = ctx.saved_tensors
         ps = ctx.ps
-        if ctx.freeze & 2 and (ctx.freeze & 1 or ps.n_coords == 3):  # only space planes take part and they are frozen
-            return None, None, None, None, None, None
         gout = gout.contiguous()
+        gpts = None
+        if ctx.needs_input_grad[6]:
+            gpts = kplanes_gather_bwd_coords(ctx.desc, planes, ctx.coords, ctx.N, gout, want_pts=True)["grad_pts"]
+        if ctx.freeze & 2 and (ctx.freeze & 1 or ps.n_coords == 3):  # only space planes take part and they are frozen
+            return None, None, None, None, None, None, gpts
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None, gpts
         gplanes = torch.zeros_like(planes)
         _lib.check(_lib.lib().snerf_kplanes_gather_bwd(C.byref(ctx.desc), _ptr(planes), C.byref(ctx.coords), C.c_int64(ctx.N), _ptr(gout),
                                                        _ptr(gplanes), _stream()), "kplanes_gather_bwd")
         if ctx.freeze & 2:
             for s in range(len(ps.resolutions)):
                 gplanes[ps.offsets[s][0]: ps.offsets[s][4]].zero_()  # XY XZ XT YZ are contiguous in the buffer
-        return gplanes, None, None, None, None, None
+        return gplanes, None, None, None, None, None, gpts
+
+
+def kplanes_gather_bwd_coords(desc: _lib.KPlanesDesc, planes, coords: _lib.Coords, N: int, grad_out, want_pts: bool = True, grad_origins=None,
+                              grad_dirs=None, stream=None):
+    """snerf_kplanes_gather_bwd_coords: the gather's gradient w.r.t. the sample coordinates.  Returns {"grad_pts": [N, n_coords] or None};
+    grad_origins / grad_dirs [R,3] (coords mode 1 only) are ACCUMULATED into when given.  The caller keeps the coordinate tensors alive."""
+    grad_out = _f32c(grad_out, "grad_out")
+    out_w = desc.C * desc.n_scales if desc.concat else desc.C
+    if grad_out.numel() != N * out_w:
+        raise RuntimeError(f"kplanes_gather_bwd_coords: grad_out has {grad_out.numel()} elements, expected {N} x {out_w}")
+    R = N // coords.S if coords.mode == 1 else 0
+    for name, t in (("grad_origins", grad_origins), ("grad_dirs", grad_dirs)):
+        if t is None:
+            continue
+        if coords.mode != 1:
+            raise RuntimeError(f"kplanes_gather_bwd_coords: {name} needs ray coordinates (mode 1)")
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (R, 3):
+            raise RuntimeError(f"kplanes_gather_bwd_coords: {name} must be a contiguous float32 HIP tensor [{R}, 3]")
+    gpts = torch.empty(N, desc.n_coords, dtype=torch.float32, device=grad_out.device) if want_pts else None
+    _lib.check(_lib.lib().snerf_kplanes_gather_bwd_coords(C.byref(desc), _ptr(planes), C.byref(coords), C.c_int64(N), _ptr(grad_out),
+                                                          _ptr(gpts) if gpts is not None else None,
+                                                          _ptr(grad_origins) if grad_origins is not None else None,
+                                                          _ptr(grad_dirs) if grad_dirs is not None else None,
+                                                          stream if stream is not None else _stream()), "kplanes_gather_bwd_coords")
+    return {"grad_pts": gpts}
 
 
 class SortedScatter:
@@ -207,12 +238,17 @@ class SortedScatter:
 
 def interpolate_kplanes(pts: torch.Tensor, plane_set: PlaneSet, freeze_time_planes: bool = False, freeze_space_planes: bool = False) -> torch.Tensor:
     """Drop-in for interpolate_kplanes(pts, ms_grids, concat_features, freeze_time_planes, freeze_space_planes) (NS/fields/kplanes_field.py:77-126).
-    pts [N,4] in [-1,1]; returns [N, C*n_scales] (concat) or [N, C]."""
+    pts [N,4] in [-1,1]; returns [N, C*n_scales] (concat) or [N, C].  A pts that requires grad receives its gradient, except with
+    freeze_space_planes, where it receives none."""
     pts = _f32c(pts, "pts")
     freeze = int(bool(freeze_time_planes)) | (int(bool(freeze_space_planes)) << 1)
     if freeze & 1 and plane_set.n_coords == 4:
         pts = pts[:, :3].contiguous()  # the static-scene view reads [N,3] points
-    return _KPlanesGather.apply(plane_set.planes, plane_set, (pts,), coords_from_points(pts), pts.shape[0], freeze)
+    # the camera optimiser's path: d/d pts through snerf_kplanes_gather_bwd_coords.  With freeze_space_planes the call behaves as it always
+    # did -- no gradient reaches pts (the reference's partial gradient through YT and ZT alone is not built)
+    if pts.requires_grad and not freeze & 2:
+        return _KPlanesGather.apply(plane_set.planes, plane_set, (pts,), coords_from_points(pts), pts.shape[0], freeze, pts)
+    return _KPlanesGather.apply(plane_set.planes, plane_set, (pts,), coords_from_points(pts), pts.shape[0], freeze, None)
 
 
 def interpolate_kplanes_rays(plane_set: PlaneSet, origins, dirs, times, ebins, aabb, rescale: bool, freeze_time_planes: bool = False,
@@ -223,7 +259,7 @@ def interpolate_kplanes_rays(plane_set: PlaneSet, origins, dirs, times, ebins, a
     R, S = ebins.shape[0], ebins.shape[1] - 1
     c = coords_from_rays(origins, dirs, times, ebins, aabb, rescale)
     freeze = int(bool(freeze_time_planes)) | (int(bool(freeze_space_planes)) << 1)
-    return _KPlanesGather.apply(plane_set.planes, plane_set, (origins, dirs, times, ebins), c, R * S, freeze)
+    return _KPlanesGather.apply(plane_set.planes, plane_set, (origins, dirs, times, ebins), c, R * S, freeze, None)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -840,6 +876,70 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
         _lib.check(_lib.lib().snerf_raygen(C.byref(a), _stream()), "raygen")
     out["camera_indices"] = indices[:, 0:1]
     return out
+
+
+def _group_table(group, M: int, dev):
+    if group is None:
+        return None
+    if not group.is_cuda or group.dtype != torch.int32 or not group.is_contiguous() or group.numel() != M:
+        raise RuntimeError(f"pose group table: expected a contiguous int32 HIP tensor [{M}]")
+    return group
+
+
+def pose_apply(c2w: torch.Tensor, pose_adjustment: torch.Tensor, group: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """snerf_pose_apply: c2w [M,3,4] composed with exp_map_SO3xR3(pose_adjustment[group]) on the right (cameras.py:707-708).  group: int32 [M]
+    with values in [0, G) -- checked by the caller, on the host -- or None for one row per camera."""
+    c2w, pose_adjustment = _f32c(c2w, "c2w"), _f32c(pose_adjustment, "pose_adjustment")
+    M, G = c2w.shape[0], pose_adjustment.shape[0]
+    if tuple(c2w.shape[1:]) != (3, 4) or tuple(pose_adjustment.shape) != (G, 6):
+        raise RuntimeError(f"pose_apply: c2w {tuple(c2w.shape)} / pose_adjustment {tuple(pose_adjustment.shape)}: expected [M,3,4] and [G,6]")
+    group = _group_table(group, M, c2w.device)
+    if group is None and G != M:
+        raise RuntimeError(f"pose_apply: {G} pose rows for {M} cameras need a group table")
+    out = torch.empty_like(c2w) if out is None else out
+    _lib.check(_lib.lib().snerf_pose_apply(_ptr(c2w), _ptr(pose_adjustment), _ptr(group) if group is not None else None, M, G, _ptr(out), _stream()),
+               "pose_apply")
+    return out
+
+
+def raygen_pose_bwd(indices, fx, fy, cx, cy, c2w, pose_adjustment, g_origins, g_dirs, grad_pose_fx, group=None, distortion_params=None,
+                    camera_type=None, dyn: Optional[torch.Tensor] = None):
+    """snerf_raygen_pose_bwd: grad_pose_fx (int64 [G,6] fixed-point cells; ops.fx_to_float converts them) += the batch's pose gradient.
+    c2w is the UNADJUSTED table; distortion_params [M,6] / [6] / None and camera_type int32 [M] / None as ops.generate_rays takes them.
+    dyn: the pose group's device-side optimiser state, whose non-finite flag the kernel raises."""
+    if not indices.is_cuda or indices.dtype != torch.int64:
+        raise RuntimeError("raygen_pose_bwd: indices must be an int64 HIP device tensor")
+    indices = indices.contiguous()
+    R, M, G = indices.shape[0], c2w.shape[0], pose_adjustment.shape[0]
+    keep = [_f32c(t, "camera table") for t in (fx, fy, cx, cy, c2w, pose_adjustment)]
+    g_origins, g_dirs = _f32c(g_origins, "g_origins"), _f32c(g_dirs, "g_dirs")
+    if tuple(g_origins.shape) != (R, 3) or tuple(g_dirs.shape) != (R, 3):
+        raise RuntimeError(f"raygen_pose_bwd: ray gradients must be [{R}, 3]")
+    if grad_pose_fx.dtype != torch.int64 or not grad_pose_fx.is_cuda or grad_pose_fx.numel() != G * 6 or not grad_pose_fx.is_contiguous():
+        raise RuntimeError(f"raygen_pose_bwd: grad_pose_fx must be a contiguous int64 HIP tensor [{G}, 6]")
+    group = _group_table(group, M, indices.device)
+    if group is None and G != M:
+        raise RuntimeError(f"raygen_pose_bwd: {G} pose rows for {M} cameras need a group table")
+    a = _lib.RaygenPoseBwdArgs()
+    a.indices = indices.data_ptr()
+    a.fx, a.fy, a.cx, a.cy, a.c2w, a.pose_adjustment = [t.data_ptr() for t in keep]
+    if distortion_params is not None:
+        distortion_params = _f32c(distortion_params, "distortion_params")
+        if tuple(distortion_params.shape) not in ((6,), (M, 6)):
+            raise RuntimeError(f"raygen_pose_bwd: distortion_params {tuple(distortion_params.shape)}: expected [6] or [{M}, 6]")
+        a.distortion, a.distortion_stride = distortion_params.data_ptr(), 6 if distortion_params.dim() == 2 else 0
+    if camera_type is not None:
+        if camera_type.dtype != torch.int32 or not camera_type.is_cuda or camera_type.numel() not in (1, M):
+            raise RuntimeError(f"raygen_pose_bwd: camera_type must be an int32 HIP tensor [{M}] or one value")
+        camera_type = camera_type.contiguous()
+        a.camera_type, a.camera_type_stride = camera_type.data_ptr(), 1 if camera_type.numel() > 1 else 0
+    if group is not None:
+        a.group = group.data_ptr()
+    a.g_origins, a.g_dirs, a.grad_pose_fx = g_origins.data_ptr(), g_dirs.data_ptr(), grad_pose_fx.data_ptr()
+    a.M, a.G, a.R = M, G, R
+    if dyn is not None:  # the pose group's device-side optimiser state (new_adam_dyn): its non-finite flag
+        a.nonfinite_flag = dyn.data_ptr()
+    _lib.check(_lib.lib().snerf_raygen_pose_bwd(C.byref(a), _stream()), "raygen_pose_bwd")
 
 
 def image_time_keys(times: torch.Tensor):

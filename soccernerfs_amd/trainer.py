@@ -147,6 +147,11 @@ class KPlanesTrainConfig:
     # the sweep pass B of the coarser scales stretches from 0.39 to 0.85 ms (fine_first), beside pass B the coarse sweep runs at 0.46 of the HBM peak instead
     # of 0.79 (coarse_first; profiles/r05_step_offsets_pipelined_*.txt).  Off: the gain is confined to the early schedule and inside the box-to-box spread.
     pipeline_sweep: str = ""
+    # Camera optimiser (camera_optimizers.py): backward() / train_step() leave d(total loss) / d(ray origins, directions) in
+    # trainer.ray_grads, from the nerf level on every step and from the two proposal levels on steps that update the proposal networks
+    # (snerf_kplanes_gather_bwd_coords; bin edges are constants).  It needs the fp32 feature gradient, so the step takes the flow without the
+    # quotient epilogue.  Off: no buffer, no launch, the step as it was.
+    ray_gradients: bool = False
 
 
 class KPlanesTrainer(FusedStep):
@@ -158,6 +163,14 @@ class KPlanesTrainer(FusedStep):
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
         # world > 1: reduce-scatter + sharded Adam + all-gather for the field planes instead of one all-reduce (see dist.py)
+        if cfg.ray_gradients:
+            # what the ray gradient does not cover raises here, by name and before anything is allocated, instead of training the poses on a
+            # partial gradient.  (The depth losses are switched on per step, by handing backward() / train_step() termination depths: refused
+            # there.  This trainer has no scene contraction, no linear decoder and no chunked backward to refuse.)
+            if not cfg.disable_viewing_dependent:
+                raise NotImplementedError("ray_gradients with disable_viewing_dependent=False is not built: the SH branch's gradient w.r.t. the ray direction")
+            if self.world > 1:
+                raise NotImplementedError("ray_gradients with world > 1 (multi-GPU) is not built: the pose gradient is not reduced across ranks")
         self.shard_optimizer = self.world > 1 and cfg.shard_optimizer
         # opt-in half-width transports of the sharded step: "bf16" rounds the field-plane gradient before the reduce-scatter /
         # gathers the parameter UPDATES in bf16; "fp32" (default) keeps the reference's DDP semantics
@@ -301,6 +314,10 @@ class KPlanesTrainer(FusedStep):
             self.buf["feat16"] = torch.empty(R * self.S[2], self.field_planes.out_dim, dtype=dt16, device=self.dev)
         self.quotient_epilogue = bool(cfg.quotient_epilogue and self.quotient_scatter and self.fused_field and self.sigma_net.desc.operands == 1
                                       and self.sigma_net.desc.hidden == 128 and self.sigma_net.desc.n_hidden == 1)
+        if cfg.ray_gradients:
+            self.quotient_epilogue = False  # the sigma_net backward writes the fp32 feature gradient (the flow of quotient_epilogue=False)
+            self.ray_grads = {"origins": torch.zeros(R, 3, dtype=torch.float32, device=self.dev),
+                              "directions": torch.zeros(R, 3, dtype=torch.float32, device=self.dev)}
         self._qg_step = False
         self.pass_b_beside_head = cfg.pass_b_beside_head
         self._in_train_step = False
@@ -697,7 +714,8 @@ class KPlanesTrainer(FusedStep):
                 L, net = levels[lvl], self.prop_nets[lvl]
                 L.desc, L.planes, L.coords = C.addressof(self._desc_prop[lvl]), self.prop_planes[lvl].planes.data_ptr(), C.addressof(self._coords[lvl])
                 L.N, L.net, L.W, L.gdens = R * self.S[lvl], C.addressof(net.desc), net.params.data_ptr(), b["gdens"][lvl].data_ptr()
-                L.grad_planes, L.workspace, L.gX = self.gviews[f"prop{lvl}.planes"].data_ptr(), self._mlp_ws[f"prop{lvl}.mlp"].data_ptr(), None
+                L.grad_planes, L.workspace = self.gviews[f"prop{lvl}.planes"].data_ptr(), self._mlp_ws[f"prop{lvl}.mlp"].data_ptr()
+                L.gX = b["gpfeat"][lvl].data_ptr() if cfg.ray_gradients else None
                 self._ws_dirty.add(f"prop{lvl}.mlp")
             with self._span("kplanes_density_bwd"):
                 _lib.check(self.lib.snerf_kplanes_density_bwd(levels, 2, self._st), "kplanes_density_bwd")
@@ -709,6 +727,18 @@ class KPlanesTrainer(FusedStep):
             for lvl in (0, 1):
                 for stage in (wb, nb, sc):
                     stage(lvl)
+        if cfg.ray_gradients:
+            # the interlevel loss reaches the rays through the proposal densities too: both levels add into ray_grads, one after the other on
+            # this stream; the nerf level adds behind them (backward())
+            for lvl in (0, 1):
+                self._ray_gradient(self._desc_prop[lvl], self.prop_planes[lvl].planes, self._coords[lvl], R * self.S[lvl], b["gpfeat"][lvl])
+
+    def _ray_gradient(self, desc, planes, coords, N, gfeat):
+        """ray_grads += d(sum gfeat . features) / d(ray origins, directions) of one sampling level (snerf_kplanes_gather_bwd_coords)."""
+        with self._span("kplanes_gather_bwd_coords.field" if desc is self._desc_field else "kplanes_gather_bwd_coords.prop"):
+            _lib.check(self.lib.snerf_kplanes_gather_bwd_coords(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gfeat), None,
+                                                                self._p(self.ray_grads["origins"]), self._p(self.ray_grads["directions"]), self._st),
+                       "kplanes_gather_bwd_coords")
 
     def backward(self, target: torch.Tensor, rng: Dict[str, torch.Tensor], proposal_grads: bool, include_reg: bool = True,
                  defer_prop_join: bool = False, depth: Optional[torch.Tensor] = None):
@@ -723,6 +753,13 @@ class KPlanesTrainer(FusedStep):
         self._reg_in_adam = not include_reg  # train_step: the regularisers' values and gradients come out of the optimiser sweep
         # depth supervision: termination depths [R] (batch["depth_image"]); None or a zero coefficient switches the term off
         self._depth = ops._f32c(depth, "depth").reshape(-1) if depth is not None and co.get("depth_loss", 0) > 0 else None
+        if cfg.ray_gradients:
+            if self._depth is not None:
+                raise NotImplementedError("ray_gradients with the depth losses is not built: their gradient w.r.t. the rays is not formed")
+            # zeroed on the caller's stream before any chain forks from it
+            self.ray_grads["origins"].zero_()
+            self.ray_grads["directions"].zero_()
+            defer_prop_join = False  # the nerf level's share is added behind the proposal levels' (fixed order: the same bits on every run)
         overlap = self.overlap
         sharded = self._sharded()  # the field-plane gradient leaves for the reduce-scatter as soon as it is complete, and the
         #                            proposal backward runs AFTER it, under the collective
@@ -793,6 +830,10 @@ class KPlanesTrainer(FusedStep):
                 self._prop_pending = st
             else:
                 main.wait_stream(st)
+        if cfg.ray_gradients:
+            # the proposal chain has been joined: its two additions to ray_grads are complete.  gfeat, the planes (the optimiser has not run) and
+            # the nerf level's coordinates are what the field backward above read.
+            self._ray_gradient(self._desc_field, self.field_planes.planes, self._coords[2], R * self.S[2], b["gfeat"])
         # weight-gradient workspaces -> self.grads: the field's nets now, the proposal nets once their chain has been joined
         self._reduce_mlp_grads(("field.sigma", "field.color"))
         if self._prop_pending is None:
@@ -1223,9 +1264,10 @@ class KPlanesTrainer(FusedStep):
                 seg = buf[off + ch["lo"]:off + ch["hi"]]
                 sdist.all_gather_shards(seg, seg[self.rank * ch["shard"]:(self.rank + 1) * ch["shard"]].clone(), self.pg)
 
-    def save_checkpoint(self, checkpoint_dir: str, save_only_latest_checkpoint: bool = True) -> Optional[str]:
+    def save_checkpoint(self, checkpoint_dir: str, save_only_latest_checkpoint: bool = True, camera_optimizer=None) -> Optional[str]:
         """Writes `step-%09d.ckpt` (rank 0 only; collective when the optimiser is sharded).  The saved step is the index of the last
-        completed iteration, as the reference saves it; load_checkpoint resumes at step + 1."""
+        completed iteration, as the reference saves it; load_checkpoint resumes at step + 1.  camera_optimizer: its pose adjustments and
+        Adam state go into the file under the reference's names (nothing is added for None or mode "off")."""
         from . import checkpoint as CK
 
         self.synchronize()
@@ -1237,15 +1279,20 @@ class KPlanesTrainer(FusedStep):
         root = self._named_module()
         hyper = {"lr": self.cfg.lr, "betas": (0.9, 0.999), "eps": self.cfg.adam_eps, "weight_decay": 0, "amsgrad": False}
         opt = CK.export_optimizer_states(root, moments, {"fields": hyper, "proposal_networks": hyper})
-        return CK.save_checkpoint(checkpoint_dir, max(self.step - 1, 0), root, opt, save_only_latest_checkpoint)
+        extra = None
+        if camera_optimizer is not None:
+            extra, cam_opt = camera_optimizer.checkpoint_entries()
+            opt.update(cam_opt)
+        return CK.save_checkpoint(checkpoint_dir, max(self.step - 1, 0), root, opt, save_only_latest_checkpoint, extra_pipeline=extra)
 
-    def load_checkpoint(self, load_dir: str, load_step: Optional[int] = None) -> int:
-        """Parameters (+ Adam moments when the file holds them) from a nerfstudio checkpoint; returns the step training resumes at."""
+    def load_checkpoint(self, load_dir: str, load_step: Optional[int] = None, camera_optimizer=None) -> int:
+        """Parameters (+ Adam moments when the file holds them) from a nerfstudio checkpoint; returns the step training resumes at.
+        camera_optimizer: takes its state from the file too (zeros when the file has none)."""
         from . import checkpoint as CK
 
         self.synchronize()
         root = self._named_module()
-        start, moments = CK.load_checkpoint(load_dir, root, load_step)
+        start, moments = CK.load_checkpoint(load_dir, root, load_step, camera_optimizer=camera_optimizer)
         names = self._ck_names()
         for ck, (m, v, _) in moments.items():
             self.mviews[names[ck]].copy_(m.reshape(-1).to(self.dev))

@@ -55,6 +55,45 @@ def eval_set(trainer, data, image_ids, anneal, with_ssim=True):
     return psnrs, ssims
 
 
+def perturb_poses(c2w, cam_id, pos_std, rot_std, seed):
+    """A seeded SE(3) perturbation of a camera table on the host, ONE per physical camera (a static stadium camera is miscalibrated the same
+    way in all of its frames): c2w' = [R exp(w) | t + dt] with w ~ N(0, rot_std^2) (radians, axis-angle) and dt ~ N(0, pos_std^2) per axis."""
+    gen = torch.Generator().manual_seed(seed)
+    ids = cam_id.cpu()
+    uniq = torch.unique(ids)
+    w = torch.randn(len(uniq), 3, generator=gen, dtype=torch.float64) * rot_std
+    dt = torch.randn(len(uniq), 3, generator=gen, dtype=torch.float64) * pos_std
+    row = torch.searchsorted(uniq, ids)
+    th = w.norm(dim=1).clamp_min(1e-12)
+    k = w / th[:, None]
+    K = torch.zeros(len(uniq), 3, 3, dtype=torch.float64)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -k[:, 2], k[:, 1], k[:, 2], -k[:, 0], -k[:, 1], k[:, 0]
+    E = torch.eye(3, dtype=torch.float64)[None] + torch.sin(th)[:, None, None] * K + (1 - torch.cos(th))[:, None, None] * (K @ K)
+    m = c2w.cpu().double()
+    out = torch.cat([m[:, :, :3] @ E[row], m[:, :, 3:] + dt[row][:, :, None]], dim=-1)
+    return out.float().to(c2w.device).contiguous()
+
+
+def pose_error(c2w, c2w_true):
+    """Error of a camera table against the true one: RMS of the camera-centre error and mean rotation angle (degrees), raw and after the rigid
+    alignment (rotation + translation, Kabsch on the camera centres) that a joint optimisation is free to apply to the whole scene."""
+    a, b = c2w.detach().cpu().double(), c2w_true.detach().cpu().double()
+
+    def figures(m):
+        d = m[:, :, 3] - b[:, :, 3]
+        rel = m[:, :, :3].transpose(1, 2) @ b[:, :, :3]
+        cos = ((rel[:, 0, 0] + rel[:, 1, 1] + rel[:, 2, 2]) - 1) / 2
+        return {"centre_rms": float(d.pow(2).sum(1).mean().sqrt()), "rotation_mean_deg": float(torch.rad2deg(torch.acos(cos.clamp(-1, 1))).mean())}
+
+    ca, cb = a[:, :, 3].mean(0), b[:, :, 3].mean(0)
+    H = (a[:, :, 3] - ca).t() @ (b[:, :, 3] - cb)
+    U, _, Vt = torch.linalg.svd(H)
+    D = torch.diag(torch.tensor([1.0, 1.0, float(torch.sign(torch.det(Vt.t() @ U.t())))], dtype=torch.float64))
+    Rg = Vt.t() @ D @ U.t()
+    aligned = torch.cat([Rg[None] @ a[:, :, :3], (Rg[None] @ (a[:, :, 3:] - ca[None, :, None])) + cb[None, :, None]], dim=-1)
+    return {"raw": figures(a), "aligned": figures(aligned)}
+
+
 def stats(xs):
     n = len(xs)
     mean = sum(xs) / n
@@ -68,7 +107,8 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
                              disable_viewing_dependent=not args.view_dependent,
                              nonfinite_policy=args.nonfinite_policy, fused_field=not args.no_fused_field, quotient_scatter=not args.no_quotient_scatter, gvec_dtype=args.gvec_dtype,
                              emulate_transports=args.emulate_transports, quotient_epilogue=not args.no_quotient_epilogue, fused_proposal=not args.no_fused_proposal,
-                             sigma_operands=args.sigma_operands, color_operands=args.color_operands, proposal_operands=args.proposal_operands)
+                             sigma_operands=args.sigma_operands, color_operands=args.color_operands, proposal_operands=args.proposal_operands,
+                             ray_gradients=args.optimize_cameras)
     R = 4096
     if args.standin:
         # the reference's algorithm in stock PyTorch (oracle/torch_standin.py: checker / baseline code, imported ONLY for this mode) on the same
@@ -93,6 +133,20 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
     DynamicBasedPixelSampler.prepare(batch, args.mask_ist)
     time_key, n_time_keys = ops.image_time_keys(train["times"])
     run = {"seed": seed, "evals": []}
+    cam_opt, cameras, c2w_given = None, None, train["c2w"]
+    if "c2w_true" in train:
+        run["pose_error_before"] = pose_error(c2w_given, train["c2w_true"])
+    if args.optimize_cameras:
+        # CameraOptimizer (SO3xR3): the training rays and the training-view evaluation go through the adjusted table; held-out cameras stay as given
+        from soccernerfs_amd.camera_optimizers import CameraOptimizer, CameraOptimizerConfig
+        from soccernerfs_amd.cameras import Cameras
+        from soccernerfs_amd.dataparsers import camera_pose_groups
+
+        cameras = Cameras(c2w_given, train["fx"], train["fy"], train["cx"], train["cy"], W, H, times=train["times"], ids=train["cam_id"],
+                          distortion_params=train.get("ray_distortion"))
+        cam_opt = CameraOptimizer(CameraOptimizerConfig(mode="SO3xR3", max_steps=args.schedule_steps), M, dev,
+                                  groups=camera_pose_groups(cameras) if args.share_poses_per_camera else None)
+        run["pose_rows"] = cam_opt.num_groups
     t_train, t_eval = 0.0, 0.0
     t_start, last_step = time.time(), args.steps - 1
     eval_at = {int(x) for x in args.eval_at.split(",") if x}
@@ -103,6 +157,8 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
         ev = {"step": step + 1}
         t2 = time.time()
         for name, (data, ids) in sets.items():
+            if name == "train" and cam_opt is not None:  # training views are rendered from where the optimiser has moved their cameras
+                data = dict(data, c2w=cam_opt.adjusted_camera_to_worlds(cameras))
             ps, ss = eval_set(trainer, data, ids, an, with_ssim=name != "train")
             ev[name] = {"psnr_mean": sum(ps) / len(ps), "psnr_min": min(ps), "images": len(ps), "psnr_per_image": [round(p, 3) for p in ps]}
             if ss:
@@ -127,9 +183,13 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
         if args.time_sorted_rays:  # the batch in order of frame time (ops.sort_rays_by_time: a batch is a set), as bench.py runs it
             idx = ops.sort_rays_by_time(idx, time_key, n_time_keys)
         target = train["images"][idx[:, 0], idx[:, 1], idx[:, 2]].float() / 255.0
-        rays = ops.generate_rays(idx, train["fx"], train["fy"], train["cx"], train["cy"], train["c2w"], train["times"], aabb=trainer.aabb,
+        table = cam_opt.adjusted_camera_to_worlds(cameras) if cam_opt is not None else train["c2w"]
+        rays = ops.generate_rays(idx, train["fx"], train["fy"], train["cx"], train["cy"], table, train["times"], aabb=trainer.aabb,
                                  near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"))
         trainer.train_step(rays, target)
+        if cam_opt is not None:
+            cam_opt.backward(idx, trainer.ray_grads)
+            cam_opt.step()
         if args.standin and step % 100 == 99:
             print(f"[standin seed {seed}] step {step + 1} {time.time() - t1:.1f}s into this thousand", flush=True)
         if step % 1000 == 999:
@@ -147,6 +207,14 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
     run["train_seconds"] = t_train
     run["train_rays_per_s_mean"] = R * ((last_step + 1) // 1000 * 1000) / max(t_train, 1e-9)
     run["skipped_steps"] = trainer.skipped_steps()
+    if cam_opt is not None:
+        run["skipped_steps"].update(cam_opt.skipped_steps())
+        adj = cam_opt.pose_adjustment.detach()
+        run["pose_adjustment_rms"] = {"translation": float(adj[:, :3].pow(2).mean().sqrt()), "rotation": float(adj[:, 3:].pow(2).mean().sqrt())}
+        if "c2w_true" in train:
+            run["pose_error_after"] = pose_error(cam_opt.adjusted_camera_to_worlds(cameras), train["c2w_true"])
+    elif "c2w_true" in train:
+        run["pose_error_after"] = run["pose_error_before"]
     trainer.synchronize()
     run["param_checksum"] = float(trainer.params.double().sum())
     run["eval_seconds"] = t_eval
@@ -202,7 +270,18 @@ def main():
                     "(synthetic.add_broadcast_overlay: constant colour + a stripe that moves with the frame time); the held-out views stay clean")
     ap.add_argument("--use-masks", action="store_true", help="with --overlay: draw the training pixels inside the banner's mask (snerf_sample_pixels_masked)")
     ap.add_argument("--mask-ist", action="store_true", help="with --use-masks: DynamicBasedPixelSampler(mask_ist_weights=True), the IST maps are zeroed outside the mask")
+    ap.add_argument("--pose-noise", default="", help="POS_STD,ROT_STD: the TRAINING camera table is perturbed on the host with a seeded SE(3) perturbation, one per "
+                    "physical camera (scene units, radians); the dataset is shot with the exact cameras and the held-out cameras stay exact")
+    ap.add_argument("--pose-noise-seed", type=int, default=7)
+    ap.add_argument("--optimize-cameras", action="store_true", help="CameraOptimizer (SO3xR3, Adam lr 6e-4, eps 1e-15) on the training cameras: "
+                    "KPlanesTrainConfig(ray_gradients=True), snerf_pose_apply / snerf_raygen_pose_bwd (DESIGN.md 4.13)")
+    ap.add_argument("--share-poses-per-camera", action="store_true", help="with --optimize-cameras: one pose adjustment per physical camera "
+                    "(dataparsers.camera_pose_groups) instead of the reference's one per image")
     args = ap.parse_args(argv)
+    if args.share_poses_per_camera and not args.optimize_cameras:
+        ap.error("--share-poses-per-camera needs --optimize-cameras")
+    if args.optimize_cameras and (args.standin or args.view_dependent):
+        ap.error("--optimize-cameras runs on the HIP trainer with disable_viewing_dependent=True")
     if args.use_masks and not args.overlay:
         ap.error("--use-masks needs --overlay")
     if args.mask_ist and not args.use_masks:
@@ -226,6 +305,12 @@ def main():
         if len(box) != 4:
             ap.error("--overlay takes four numbers: Y0,Y1,X0,X1")
         train["mask"] = synthetic.add_broadcast_overlay(train, box)
+    if args.pose_noise:
+        std = [float(v) for v in args.pose_noise.split(",")]
+        if len(std) != 2:
+            ap.error("--pose-noise takes two numbers: POS_STD,ROT_STD")
+        train["c2w_true"] = train["c2w"]
+        train["c2w"] = perturb_poses(train["c2w"], train["cam_id"], std[0], std[1], args.pose_noise_seed)
     for data in (train, held, novel):  # the rows the rays of training and evaluation go through: the dataset's own, or none with --ignore-lens
         data["ray_distortion"] = None if args.ignore_lens else data.get("distortion")
     t0 = time.time()
@@ -246,6 +331,8 @@ def main():
            "deterministic": args.deterministic, "view_dependent": args.view_dependent, "nonfinite_policy": args.nonfinite_policy,
            "emulate_transports": args.emulate_transports, "time_sorted_rays": args.time_sorted_rays, "fused_field": not args.no_fused_field, "quotient_scatter": not args.no_quotient_scatter,
            "quotient_epilogue": not args.no_quotient_epilogue, "fused_proposal": not args.no_fused_proposal,
+           "pose_noise": args.pose_noise or None, "pose_noise_seed": args.pose_noise_seed if args.pose_noise else None,
+           "optimize_cameras": args.optimize_cameras, "share_poses_per_camera": args.share_poses_per_camera,
            "eval_sets": {"camera_20": "20th arc camera (reference 'all' split eval camera; extrapolated view), %d frames" % len(sets["camera_20"][1]),
                          "novel": "3 evaluation-only cameras between training cameras (interpolated views), %d images" % len(sets["novel"][1]),
                          "train": "4 training images"},

@@ -14,7 +14,7 @@
 // so host, kernel and oracle agree on it bit for bit.
 #include <math.h>
 
-#include "common.hpp"
+#include "hashgrid_common.hpp"  // ht_level, ht_cell (shared with hashgrid_tiles.hip); sets no contraction mode: `acc += w * table` below fuses as before
 
 namespace snerf {
 
@@ -48,36 +48,15 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(HgArgs a) {
   const int xb = li / F;   // this lane's low corner bits (backward): x first
   const int level = blockIdx.y + a.level0;
   if (b >= a.B) return;  // B * F is a multiple of F: the F lanes of a sample leave together
-  const float scale = a.d.scale[level];
-  const uint32_t resolution = (uint32_t)a.d.resolution[level];
-  const uint32_t off0 = (uint32_t)a.d.offsets[level];
-  const uint32_t rows = (uint32_t)(a.d.offsets[level + 1] - a.d.offsets[level]);
+  const TableLevel lv = ht_level(a.d, level, D);
+  const float scale = lv.scale;
 
   float pos[3];
   uint32_t pg[3];
-  for (int d = 0; d < D; ++d) {
-    const float p = fmaf(scale, a.x[b * D + d], 0.5f);  // pos_fract
-    const float f = floorf(p);
-    pg[d] = (uint32_t)(int)f;
-    pos[d] = p - f;
-  }
+  ht_cell(lv, a.x + b * D, D, pg, pos);
   // grid_index: per-axis terms shared by the 2^D corners (dense stride or hash prime), XOR / sum per corner, one reduction mod rows
-  const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
   uint32_t term[3][2];
-  bool hashed;
-  {
-    uint64_t stride = 1;
-    for (int d = 0; d < D && stride <= rows; ++d) stride *= resolution;
-    hashed = rows < stride;
-    uint64_t st = 1;
-    for (int d = 0; d < D; ++d) {
-      const uint32_t m = hashed ? primes[d] : (st <= rows ? (uint32_t)st : 0u);
-      term[d][0] = pg[d] * m;
-      term[d][1] = (pg[d] + 1u) * m;
-      if (st <= rows) st *= resolution;
-    }
-  }
-  const bool pow2 = (rows & (rows - 1u)) == 0u;
+  lv.corner_terms(pg, D, term);
 
   float g = 0.f;
   if (BWD) g = a.gout[b * (a.d.L * F) + level * F + fl];
@@ -88,15 +67,8 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(HgArgs a) {
   if (BWD && xb >= (1 << cb)) g = 0.f;  // D < HG_CB: surplus lanes contribute nothing (they stay for the lane exchanges below)
   for (int sub = 0; sub < ncorner; ++sub) {
     const int idx = (sub << cb) | (xb & ((1 << cb) - 1));
-    float w = 1.f;
-    uint32_t index = 0;
-    for (int d = 0; d < D; ++d) {
-      const int bit = (idx >> d) & 1;
-      w *= bit ? pos[d] : 1.f - pos[d];
-      index = hashed ? (index ^ term[d][bit]) : (index + term[d][bit]);
-    }
-    const uint32_t row = pow2 ? (index & (rows - 1u)) : (index % rows);
-    const size_t e = ((size_t)off0 + row) * F;
+    const float w = table_corner_weight(pos, D, idx);
+    const size_t e = ((size_t)lv.off0 + lv.row_of_corner(term, D, idx)) * F;
     if (!BWD) {
 #pragma unroll
       for (int f = 0; f < F; ++f) acc[f] += w * a.table[e + f];

@@ -8,7 +8,8 @@
 // Adam over them from there (MODE 1: no dense gradient for this table) or adds them into the dense gradient with plain stores (MODE 0).  The coordinate gradient
 // (the deformation net's input) stays with hashgrid_kernel, called without a table gradient: it is a gather.
 #include "plane_adam_common.hpp"  // adam_float4, ldnt4 / stnt4: compiled with the optimiser sweep's own contraction setting
-#include "table_tiles_common.hpp"  // no contraction from here on: cells and weights exactly as hashgrid.hip derives them
+#include "hashgrid_common.hpp"     // ht_level, ht_cell: the level and cell that hashgrid.hip derives too
+#include "table_tiles_common.hpp"  // no contraction from here on
 
 namespace snerf {
 
@@ -20,47 +21,18 @@ struct HtArgs : TileCoreArgs {
   float step_size, b1, b2, inv_sqrt_bc2, eps;
 };
 
-// grid_index of hashgrid_kernel: per-axis multipliers (dense stride or hash prime), one reduction modulo the level's rows
-__device__ __forceinline__ TableLevel ht_level(const snerf_hashgrid_desc& d, int level) {
-  TableLevel lv;
-  lv.off0 = (uint32_t)d.offsets[level];
-  lv.rows = (uint32_t)(d.offsets[level + 1] - d.offsets[level]);
-  lv.scale = d.scale[level];
-  const uint32_t resolution = (uint32_t)d.resolution[level];
-  const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
-  uint64_t stride = 1;
-  for (int k = 0; k < 3 && stride <= lv.rows; ++k) stride *= resolution;
-  lv.hashed = lv.rows < stride;
-  uint64_t st = 1;
-  for (int k = 0; k < 3; ++k) {
-    lv.mult[k] = lv.hashed ? primes[k] : (st <= lv.rows ? (uint32_t)st : 0u);
-    if (st <= lv.rows) st *= resolution;
-  }
-  lv.pow2 = (lv.rows & (lv.rows - 1u)) == 0u;
-  return lv;
-}
-__device__ __forceinline__ void ht_cell(const TableLevel& lv, const float* x, uint32_t pg[3], float fr[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float p = fmaf(lv.scale, x[k], 0.5f);  // pos_fract, as hashgrid_kernel
-    const float f = floorf(p);
-    pg[k] = (uint32_t)(int)f;
-    fr[k] = p - f;
-  }
-}
-
 // the static hash grid's tile policy (table_tiles_common.hpp)
 template <int F>
 struct HtTiles {
   HtArgs a;
   __host__ __device__ int levels() const { return a.d.L; }
   __host__ __device__ int row_floats() const { return F; }
-  __device__ __forceinline__ TableLevel level(int l) const { return ht_level(a.d, l); }
+  __device__ __forceinline__ TableLevel level(int l) const { return ht_level(a.d, l, 3); }
 
   __device__ __forceinline__ bool cell(const TableLevel& lv, int l, int64_t b, uint32_t pg[3], float fr[3]) const {
     if (tile_gradient_is_zero<F>(a, a.d.L, l, b)) return false;
     const float x[3] = {a.x[b * 3], a.x[b * 3 + 1], a.x[b * 3 + 2]};  // no bounds check on coordinates, as tcnn
-    ht_cell(lv, x, pg, fr);
+    ht_cell(lv, x, 3, pg, fr);
     return true;
   }
 
@@ -71,7 +43,7 @@ struct HtTiles {
   __device__ __forceinline__ Sample sample(const Rec& rc, const TableLevel& lv, int l, uint32_t pg[3], float fr[3]) const {
     const int64_t b = (int64_t)(rc.rec >> 4);
     const float x[3] = {a.x[b * 3], a.x[b * 3 + 1], a.x[b * 3 + 2]};
-    ht_cell(lv, x, pg, fr);
+    ht_cell(lv, x, 3, pg, fr);
     const float* gp = a.gout + b * (a.d.L * F) + l * F;
     Sample s;
 #pragma unroll

@@ -287,10 +287,7 @@ __device__ __forceinline__ void tile_walk(const P& p, TileWalk<P>& w, const Tile
 #pragma unroll
     for (int xb = 0; xb < 2; ++xb) {
       if (!((xm >> xb) & 1)) continue;
-      float wgt = 1.f;  // the corner's weight, factors in axis order as the scatter kernels multiply them
-      wgt *= xb ? fr[0] : 1.f - fr[0];
-      wgt *= (yz & 1) ? fr[1] : 1.f - fr[1];
-      wgt *= (yz >> 1) ? fr[2] : 1.f - fr[2];
+      const float wgt = table_corner_weight(fr, 3, xb | (yz << 1));  // the scatter kernels' own
       const uint32_t row = lv.row_of(pg[0] + (uint32_t)xb, cy, cz);
       p.add(smp, acc + s.ph + (int)(row - s.row0) * p.row_floats(), wgt);
     }

@@ -14,7 +14,7 @@
 //  * sample coordinates can be derived in-kernel from rays (snerf_coords mode 1), as for the K-Planes gather.
 #include <stdlib.h>
 
-#include "tgrid_common.hpp"  // tg_slot_from_time (shared with tgrid_tiles.hip)
+#include "tgrid_common.hpp"  // time slot, level, sample position and cell (shared with tgrid_tiles.hip)
 
 // No fused multiply-adds formed by contraction in this file: the run-length kernels below promise the per-sample kernels' results BIT FOR BIT, and
 // which a * b + c the compiler fuses depends on the code around it (the first run-length forward differed from tgrid_kernel<false> by 1 ulp in ray
@@ -56,22 +56,15 @@ __global__ __launch_bounds__(256) void tgrid_kernel(TgridArgs a) {
   const bool live = b < a.B;
   const int64_t bb = live ? b : a.B - 1;
 
-  // ---- coordinates in [0,1] ----
+  // ---- coordinates in [0,1] (tg_sample_x's, for any D and with a 64-bit sample index) ----
   float x[3] = {0.f, 0.f, 0.f};
   if (a.c.mode == 0) {
     for (int d = 0; d < D; ++d) x[d] = a.c.pts[bb * D + d];
   } else {
     const int64_t r = bb / a.c.S;
-    const int s = (int)(bb - r * a.c.S);
-    const float* eb = a.c.ebins + r * (a.c.S + 1) + s;
-    const float mid = eb[0] + eb[1];
-    for (int d = 0; d < 3; ++d) {
-      float pos = a.c.origins[r * 3 + d] + (a.c.dirs[r * 3 + d] * mid) / 2.f;
-      x[d] = (pos - a.c.aabb_min[d]) / (a.c.aabb_max[d] - a.c.aabb_min[d]);
-    }
+    tg_ray_sample_x(a.c, r, (int)(bb - r * a.c.S), x);
   }
-  bool oob = false;
-  for (int d = 0; d < D; ++d) oob |= (x[d] < 0.f) || (x[d] > 1.f);  // .cu:119-124
+  const bool oob = tg_out_of_range(x, D);
 
   // ---- this lane's column and temporal weight ----
   int col;
@@ -86,18 +79,10 @@ __global__ __launch_bounds__(256) void tgrid_kernel(TgridArgs a) {
     tg_slot_from_time(a.times[trow_i], C, a.d.grid_C - C - 1, ch, ab, col, wt);
   }
 
-  const uint32_t off0 = (uint32_t)a.d.offsets[level];
-  const uint32_t hashmap_size = (uint32_t)(a.d.offsets[level + 1] - a.d.offsets[level]);
-  const float scale = exp2f((float)level * a.d.S) * (float)a.d.H - 1.0f;  // .cu:146-148
-  const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
+  const TgLevel lv = tg_level(a.d, level, D);
   float pos[3];
   uint32_t pg[3];
-  for (int d = 0; d < D; ++d) {
-    pos[d] = x[d] * scale + (a.d.align_corners ? 0.0f : 0.5f);
-    float f = floorf(pos[d]);
-    pg[d] = (uint32_t)f;
-    pos[d] -= f;
-  }
+  tg_cell(lv, a.d.align_corners != 0, x, D, pg, pos);
 
   float g = 0.f;
   if (BWD) g = a.gout[bb * (a.d.L * C) + level * C + ch] * wt;
@@ -105,36 +90,14 @@ __global__ __launch_bounds__(256) void tgrid_kernel(TgridArgs a) {
   float acc = 0.f;
   float dacc[3] = {0.f, 0.f, 0.f};  // DYDX: d (this lane's column share of the output) / d x_d
   const int ncorner = 1 << D;
-  // Row index of a corner = get_grid_index (.cu:62-88): fast_hash (XOR of coordinate * prime, .cu:46-59) on hashed levels, the
-  // strided sum on dense ones, modulo the level's table size.  Per-axis terms, shared by the 2^D corners: t[d][bit] = (pg[d] + bit) * (prime[d] | dense stride[d]); a corner's row is
-  // their XOR (hashed level) or sum (dense level), then one reduction modulo the table size -- a mask when the size is a power of two
-  // (every hashed level: 2^log2_hashmap_size).  Same values as get_grid_index (.cu:62-88), a third of the integer work.
-  const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
+  // Row index of a corner = get_grid_index (.cu:62-88): fast_hash (XOR of coordinate * prime, .cu:46-59) on hashed levels, the strided sum on dense
+  // ones, modulo the level's table size -- TableLevel's, with the per-axis products shared by the 2^D corners.
   uint32_t term[3][2];
-  bool hashed;
-  {
-    uint32_t stride = 1;
-    for (int d = 0; d < D && stride <= hashmap_size; ++d) stride *= a.d.align_corners ? resolution : (resolution + 1);
-    hashed = a.d.gridtype == 0 && stride > hashmap_size;
-    uint32_t st = 1;
-    for (int d = 0; d < D; ++d) {
-      const uint32_t m = hashed ? primes[d] : (st <= hashmap_size ? st : 0u);  // dense: axes beyond the overflowing stride do not contribute (.cu:70-74)
-      term[d][0] = pg[d] * m;
-      term[d][1] = (pg[d] + 1u) * m;
-      if (st <= hashmap_size) st *= a.d.align_corners ? resolution : (resolution + 1);
-    }
-  }
-  const bool pow2 = (hashmap_size & (hashmap_size - 1u)) == 0u;
+  lv.corner_terms(pg, D, term);
+  const float scale = lv.scale;
   for (int idx = 0; idx < ncorner; ++idx) {
-    float w = 1.f;
-    uint32_t index = 0;
-    for (int d = 0; d < D; ++d) {
-      const int bit = (idx >> d) & 1;
-      w *= bit ? pos[d] : 1.f - pos[d];
-      index = hashed ? (index ^ term[d][bit]) : (index + term[d][bit]);
-    }
-    const uint32_t row = pow2 ? (index & (hashmap_size - 1u)) : (index % hashmap_size);
-    const size_t e = ((size_t)off0 + row) * (size_t)a.d.grid_C + (size_t)col;
+    const float w = table_corner_weight(pos, D, idx);
+    const size_t e = ((size_t)lv.off0 + lv.row_of_corner(term, D, idx)) * (size_t)a.d.grid_C + (size_t)col;
     if (active) {
       if (BWD) {
         float v = w * g;
@@ -169,7 +132,7 @@ __global__ __launch_bounds__(256) void tgrid_kernel(TgridArgs a) {
   }
 }
 
-// ---- backward, run-length form (round 4): samples of ONE ray, per-ray times (what the fused trainers hand over) ----
+// ---- run-length form (backward: round 4, forward: round 5): samples of ONE ray, per-ray times (what the fused trainers hand over) ----
 // tgrid_kernel<true> issues one float atomic per (sample, level, corner, live column): 20.7 M 64-B requests per step of config 4, and the pass runs AT the
 // chip-wide float-atomic rate (1.2 TB/s of written bytes, profiles/r04_kernels.md section 7).  Consecutive samples of a ray fall into the same cell on
 // every level whose cells are wider than the sample spacing -- all of them for the proposal grids (max_res 64 / 256 against 256 / 96 samples per ray),
@@ -181,144 +144,26 @@ constexpr int TG_RUN = 32;  // samples per segment (a ray of S samples = ceil(S 
 // RAYS: snerf_coords mode 1 (a segment lies inside one ray: origin, direction and the time slot are loaded once); otherwise explicit points [B,3] in
 // sample order with times[b / spr] -- the full NeRFPlayer's deformed positions: consecutive points are still consecutive samples of a ray with one time,
 // and where they are not, the (cell, column) key changes and the sum is sent, so any input order is handled correctly.
-template <bool RAYS>
-__global__ __launch_bounds__(256) void tgrid_bwd_runs_kernel(TgridArgs a, int segs, int run) {
+//
+// The forward (round 5) is the same walk.  tgrid_kernel<false> fetches 8 corner rows per (sample, level) even where consecutive samples of a ray stay in
+// one cell: 3.50 GB of counter traffic for 0.99 GB algorithmic on config 4 (profiles/r04_nerfplayer_fused_pmc.csv), each corner its own 64-B sector of a
+// 264-B row for <= 3 live floats.  The lane group keeps the eight corner VALUES of the current cell in registers and reloads them only when the cell or
+// the live column changes.  Per sample the arithmetic is tgrid_kernel<false>'s own -- same weights, same products, same order of the eight additions,
+// the same pair sum of the a | b columns -- so the outputs are bit-identical (tests/test_gpu_tgrid.py).
+//
+// One template for both: prologue (segment, time slot, level, ray) and the per-sample cell are shared; BWD selects what the eight registers hold (sums
+// to send | values loaded) and the per-sample body.  One difference is deliberate: the backward RETURNS for a group past the end and for a (channel,
+// column) slot that is dead for the whole ray -- nothing of it is ever sent -- while the forward must keep such lanes running (with an empty segment, or
+// adding nothing), because its pair sum is a cross-lane operation of a full wave and lane ab = 0 still has the output to write.
+template <bool BWD, bool RAYS>
+__global__ __launch_bounds__(256) void tgrid_runs_kernel(TgridArgs a, int segs, int run) {
   const int C = a.d.C, LPG = 2 * C;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t grp = gid / LPG;
   const int k = (int)(gid - grp * LPG);
   const int ch = k >> 1, ab = k & 1;
   const int level = blockIdx.y + a.level0;
-  int64_t b0, b1, r = 0;
-  if (RAYS) {
-    const int S = a.c.S;
-    r = grp / segs;
-    const int seg = (int)(grp - r * segs);
-    if (r >= a.B / S) return;
-    const int s0 = seg * run, s1 = (s0 + run) < S ? (s0 + run) : S;
-    b0 = r * S + s0; b1 = r * S + s1;
-  } else {
-    b0 = grp * run;
-    if (b0 >= a.B) return;
-    b1 = (b0 + run) < a.B ? (b0 + run) : a.B;
-  }
-  const int n_rows = a.d.grid_C - C - 1;
-  int col = 0;
-  float wt = 0.f;
-  if (RAYS) {
-    tg_slot_from_time(a.times[r], C, n_rows, ch, ab, col, wt);
-    if (wt == 0.f) return;  // this (channel, column) slot is dead for the whole ray
-  }
-
-  const uint32_t off0 = (uint32_t)a.d.offsets[level];
-  const uint32_t hashmap_size = (uint32_t)(a.d.offsets[level + 1] - a.d.offsets[level]);
-  const float scale = exp2f((float)level * a.d.S) * (float)a.d.H - 1.0f;
-  const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
-  const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
-  uint32_t mult[3];
-  bool hashed;
-  {
-    uint32_t stride = 1;
-    for (int d = 0; d < 3 && stride <= hashmap_size; ++d) stride *= a.d.align_corners ? resolution : (resolution + 1);
-    hashed = a.d.gridtype == 0 && stride > hashmap_size;
-    uint32_t st = 1;
-    for (int d = 0; d < 3; ++d) {
-      mult[d] = hashed ? primes[d] : (st <= hashmap_size ? st : 0u);
-      if (st <= hashmap_size) st *= a.d.align_corners ? resolution : (resolution + 1);
-    }
-  }
-  const bool pow2 = (hashmap_size & (hashmap_size - 1u)) == 0u;
-  float o[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f}, inv[3] = {1.f, 1.f, 1.f};
-  const float* eb = nullptr;
-  if (RAYS) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      o[d] = a.c.origins[r * 3 + d];
-      dir[d] = a.c.dirs[r * 3 + d];
-      inv[d] = a.c.aabb_max[d] - a.c.aabb_min[d];
-    }
-    eb = a.c.ebins + r * (a.c.S + 1) - r * a.c.S;  // eb[b] = edge s of ray r for b = r S + s
-  }
-  const int gstride = a.d.L * C;
-  const float* gp = a.gout + level * C + ch;
-
-  uint32_t ppg[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};  // no cell: floor() of a coordinate in [0, scale + 0.5] never gives this
-  int pcol = col;
-  float acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-  auto flush = [&]() {
-#pragma unroll
-    for (int idx = 0; idx < 8; ++idx) {
-      if (acc[idx] != 0.f) {
-        uint32_t index = 0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          const uint32_t t = (ppg[d] + ((idx >> d) & 1)) * mult[d];
-          index = hashed ? (index ^ t) : (index + t);
-        }
-        const uint32_t row = pow2 ? (index & (hashmap_size - 1u)) : (index % hashmap_size);
-        tg_grad_add(a, ((size_t)off0 + row) * (size_t)a.d.grid_C + (size_t)pcol, acc[idx]);
-        acc[idx] = 0.f;
-      }
-    }
-  };
-  for (int64_t b = b0; b < b1; ++b) {
-    if (!RAYS) tg_slot_from_time(a.times[b / a.spr], C, n_rows, ch, ab, col, wt);
-    const float g = gp[b * gstride] * wt;
-    float pos[3];
-    uint32_t pg[3];
-    bool oob = false;
-    float mid = 0.f;
-    if (RAYS) mid = eb[b] + eb[b + 1];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float x;
-      if (RAYS) {
-        const float p = o[d] + (dir[d] * mid) / 2.f;
-        x = (p - a.c.aabb_min[d]) / inv[d];
-      } else {
-        x = a.c.pts[b * 3 + d];
-      }
-      oob |= (x < 0.f) || (x > 1.f);
-      pos[d] = x * scale + (a.d.align_corners ? 0.0f : 0.5f);
-      const float f = floorf(pos[d]);
-      pg[d] = (uint32_t)f;
-      pos[d] -= f;
-    }
-    if (oob || g == 0.f) continue;  // out-of-range samples get no gradient (.cu:119-124); nothing to add
-    if (pg[0] != ppg[0] || pg[1] != ppg[1] || pg[2] != ppg[2] || col != pcol) {
-      flush();
-      ppg[0] = pg[0]; ppg[1] = pg[1]; ppg[2] = pg[2];
-      pcol = col;
-    }
-#pragma unroll
-    for (int idx = 0; idx < 8; ++idx) {
-      float w = 1.f;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) w *= ((idx >> d) & 1) ? pos[d] : 1.f - pos[d];
-      acc[idx] += w * g;
-    }
-  }
-  flush();
-}
-
-// ---- forward, run-length form (round 5): the same walk as tgrid_bwd_runs_kernel ----
-// tgrid_kernel<false> fetches 8 corner rows per (sample, level) even where consecutive samples of a ray stay in one cell: 3.50 GB of counter traffic for
-// 0.99 GB algorithmic on config 4 (profiles/r04_nerfplayer_fused_pmc.csv), each corner its own 64-B sector of a 264-B row for <= 3 live floats.  Here the
-// lane group that walks a segment of <= 32 consecutive samples keeps the eight corner values of the current cell in
-// registers and reloads them only when the cell or the live column changes.  Per sample the arithmetic is tgrid_kernel<false>'s own -- same weights, same
-// products, same order of the eight additions, the same pair sum of the a | b columns -- so the outputs are bit-identical (tests/test_gpu_tgrid.py).
-template <bool RAYS>
-__global__ __launch_bounds__(256) void tgrid_fwd_runs_kernel(TgridArgs a, int segs, int run) {
-  const int C = a.d.C, LPG = 2 * C;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t grp = gid / LPG;
-  const int k = (int)(gid - grp * LPG);
-  const int ch = k >> 1, ab = k & 1;
-  const int level = blockIdx.y + a.level0;
-  // a group past the end keeps running with an empty segment: the pair sum below is a cross-lane operation of a full wave
-  int64_t b0 = 0, b1 = 0, r = 0;
+  int64_t b0 = 0, b1 = 0, r = 0;  // past the end: the empty segment [0, 0) of ray 0
   if (RAYS) {
     const int S = a.c.S;
     r = grp / segs;
@@ -327,105 +172,106 @@ __global__ __launch_bounds__(256) void tgrid_fwd_runs_kernel(TgridArgs a, int se
       const int s0 = seg * run, s1 = (s0 + run) < S ? (s0 + run) : S;
       b0 = r * S + s0; b1 = r * S + s1;
     } else {
+      if (BWD) return;
       r = 0;
     }
   } else {
     b0 = grp * run;
-    if (b0 < a.B) b1 = (b0 + run) < a.B ? (b0 + run) : a.B; else b0 = 0;
+    if (b0 < a.B) {
+      b1 = (b0 + run) < a.B ? (b0 + run) : a.B;
+    } else {
+      if (BWD) return;
+      b0 = 0;
+    }
   }
   const int n_rows = a.d.grid_C - C - 1;
   int col = 0;
   float wt = 0.f;
-  if (RAYS) tg_slot_from_time(a.times[r], C, n_rows, ch, ab, col, wt);
-
-  const uint32_t off0 = (uint32_t)a.d.offsets[level];
-  const uint32_t hashmap_size = (uint32_t)(a.d.offsets[level + 1] - a.d.offsets[level]);
-  const float scale = exp2f((float)level * a.d.S) * (float)a.d.H - 1.0f;
-  const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
-  const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
-  uint32_t mult[3];
-  bool hashed;
-  {
-    uint32_t stride = 1;
-    for (int d = 0; d < 3 && stride <= hashmap_size; ++d) stride *= a.d.align_corners ? resolution : (resolution + 1);
-    hashed = a.d.gridtype == 0 && stride > hashmap_size;
-    uint32_t st = 1;
-    for (int d = 0; d < 3; ++d) {
-      mult[d] = hashed ? primes[d] : (st <= hashmap_size ? st : 0u);
-      if (st <= hashmap_size) st *= a.d.align_corners ? resolution : (resolution + 1);
-    }
+  if (RAYS) {
+    tg_slot_from_time(a.times[r], C, n_rows, ch, ab, col, wt);
+    if (BWD && wt == 0.f) return;
   }
-  const bool pow2 = (hashmap_size & (hashmap_size - 1u)) == 0u;
-  float o[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f}, inv[3] = {1.f, 1.f, 1.f};
+
+  const TgLevel lv = tg_level(a.d, level, 3);
+  const bool align = a.d.align_corners != 0;
+  float o[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f}, ext[3] = {1.f, 1.f, 1.f};
   const float* eb = nullptr;
   if (RAYS) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       o[d] = a.c.origins[r * 3 + d];
       dir[d] = a.c.dirs[r * 3 + d];
-      inv[d] = a.c.aabb_max[d] - a.c.aabb_min[d];
+      ext[d] = a.c.aabb_max[d] - a.c.aabb_min[d];
     }
     eb = a.c.ebins + r * (a.c.S + 1) - r * a.c.S;  // eb[b] = edge s of ray r for b = r S + s
   }
-  const int ostride = a.d.L * C;
-  float* op = a.out + level * C + ch;
+  const int stride = a.d.L * C;  // of out and grad_out alike
+  const int64_t at = level * C + ch;
 
-  uint32_t ppg[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};  // no cell yet
-  int pcol = -1;
-  float val[8];
+  uint32_t ppg[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};  // no cell yet: floor() of a coordinate in [0, scale + 0.5] never gives this
+  int pcol = col;
+  float reg[8];  // per corner of the current (cell, column) -- BWD: the sum not yet sent; forward: the table value
 #pragma unroll
-  for (int i = 0; i < 8; ++i) val[i] = 0.f;
+  for (int i = 0; i < 8; ++i) reg[i] = 0.f;
+  auto entry = [&](const uint32_t cell[3], int idx, int column) {
+    const uint32_t row = lv.row_of(cell[0] + (uint32_t)(idx & 1), cell[1] + (uint32_t)((idx >> 1) & 1), cell[2] + (uint32_t)(idx >> 2));
+    return ((size_t)lv.off0 + row) * (size_t)a.d.grid_C + (size_t)column;
+  };
+  auto flush = [&]() {
+#pragma unroll
+    for (int idx = 0; idx < 8; ++idx) {
+      if (reg[idx] != 0.f) {
+        tg_grad_add(a, entry(ppg, idx, pcol), reg[idx]);
+        reg[idx] = 0.f;
+      }
+    }
+  };
   for (int64_t b = b0; b < b1; ++b) {
     if (!RAYS) tg_slot_from_time(a.times[b / a.spr], C, n_rows, ch, ab, col, wt);
-    float pos[3];
+    float g = 0.f;
+    if (BWD) g = a.gout[b * stride + at] * wt;  // requested here, in front of the cell arithmetic that does not need it
+    float x[3], fr[3];
     uint32_t pg[3];
-    bool oob = false;
-    float mid = 0.f;
-    if (RAYS) mid = eb[b] + eb[b + 1];
+    if (RAYS) {
+      const float mid = eb[b] + eb[b + 1];
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      float x;
-      if (RAYS) {
-        const float p = o[d] + (dir[d] * mid) / 2.f;
-        x = (p - a.c.aabb_min[d]) / inv[d];
-      } else {
-        x = a.c.pts[b * 3 + d];
-      }
-      oob |= (x < 0.f) || (x > 1.f);
-      pos[d] = x * scale + (a.d.align_corners ? 0.0f : 0.5f);
-      const float f = floorf(pos[d]);
-      pg[d] = (uint32_t)f;
-      pos[d] -= f;
+      for (int d = 0; d < 3; ++d) x[d] = tg_ray_x(o[d], dir[d], mid, a.c.aabb_min[d], ext[d]);
+    } else {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) x[d] = a.c.pts[b * 3 + d];
     }
-    float acc = 0.f;
-    if (!oob && wt != 0.f) {  // tgrid_kernel's `active`: an out-of-range sample reads nothing, a dead (channel, column) slot adds nothing
-      if (pg[0] != ppg[0] || pg[1] != ppg[1] || pg[2] != ppg[2] || col != pcol) {
-#pragma unroll
-        for (int idx = 0; idx < 8; ++idx) {
-          uint32_t index = 0;
-#pragma unroll
-          for (int d = 0; d < 3; ++d) {
-            const uint32_t t = (pg[d] + ((idx >> d) & 1)) * mult[d];
-            index = hashed ? (index ^ t) : (index + t);
-          }
-          const uint32_t row = pow2 ? (index & (hashmap_size - 1u)) : (index % hashmap_size);
-          val[idx] = a.emb[((size_t)off0 + row) * (size_t)a.d.grid_C + (size_t)col];
-        }
+    const bool oob = tg_out_of_range(x, 3);
+    tg_cell(lv, align, x, 3, pg, fr);
+    const bool moved = pg[0] != ppg[0] || pg[1] != ppg[1] || pg[2] != ppg[2] || col != pcol;
+    if (BWD) {
+      if (oob || g == 0.f) continue;  // out-of-range samples get no gradient (.cu:119-124); nothing to add
+      if (moved) {
+        flush();
         ppg[0] = pg[0]; ppg[1] = pg[1]; ppg[2] = pg[2];
         pcol = col;
       }
 #pragma unroll
-      for (int idx = 0; idx < 8; ++idx) {
-        float w = 1.f;
+      for (int idx = 0; idx < 8; ++idx) reg[idx] += table_corner_weight(fr, 3, idx) * g;
+    } else {
+      float acc = 0.f;
+      if (!oob && wt != 0.f) {  // tgrid_kernel's `active`: an out-of-range sample reads nothing, a dead (channel, column) slot adds nothing
+        if (moved) {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) w *= ((idx >> d) & 1) ? pos[d] : 1.f - pos[d];
-        const float v = val[idx] * wt;  // the temporal weight is applied per sample (explicit points: every sample has its own time), as tgrid_kernel does
-        acc += w * v;
+          for (int idx = 0; idx < 8; ++idx) reg[idx] = a.emb[entry(pg, idx, col)];
+          ppg[0] = pg[0]; ppg[1] = pg[1]; ppg[2] = pg[2];
+          pcol = col;
+        }
+#pragma unroll
+        for (int idx = 0; idx < 8; ++idx) {
+          const float v = reg[idx] * wt;  // the temporal weight is applied per sample (explicit points: every sample has its own time), as tgrid_kernel does
+          acc += table_corner_weight(fr, 3, idx) * v;
+        }
       }
+      acc += __shfl_xor(acc, 1, 64);  // column a + column b of this channel: a pair shares its group, hence its segment and trip count (see the launcher)
+      if (ab == 0) a.out[b * stride + at] = oob ? 0.f : acc;
     }
-    acc += __shfl_xor(acc, 1, 64);  // column a + column b of this channel (segments of a wave's groups have the same length: see the launcher)
-    if (ab == 0) op[b * ostride] = oob ? 0.f : acc;
   }
+  if (BWD) flush();
 }
 
 static int validate(const snerf_tgrid_desc* d, const snerf_coords* c, const float* trow, const float* times, int spr, int64_t B) {
@@ -477,38 +323,22 @@ static int launch(const TgridArgs& a_in, hipStream_t st) {
   if (a.level1 > 0) { lv_lo = a.level0; lv_hi = a.level1; }
   a.level0 = lv_lo;
   const unsigned n_lv = (unsigned)(lv_hi - lv_lo);
-  if (BWD && a.d.D == 3 && a.times && !a.trow && !tgrid_runs_off()) {
-    // times instead of explicit temporal rows (every caller but the reference-shaped API test): the run-length form
+  if (!a.dy_dx && a.d.D == 3 && a.times && !a.trow && !tgrid_runs_off()) {
+    // times instead of explicit temporal rows (every caller but the reference-shaped API test): the run-length form, forward and backward over the same
+    // segments.  The forward's pair sum (__shfl_xor) needs both lanes of a (channel) pair in the same loop iteration: a pair shares its group and hence
+    // its segment, so its trip count -- whatever other groups of the wave do.
     if (a.c.mode == 1 && a.spr == a.c.S && a.B % a.c.S == 0) {  // rays: segments inside a ray
       const int S = a.c.S;
       const int segs = (S + TG_RUN - 1) / TG_RUN, run = (S + segs - 1) / segs;  // (segments of 8 ... 256 samples: 4.03 - 4.07 ms per step of config 4, no trend)
       const int64_t threads = (a.B / S) * segs * 2 * a.d.C;
-      hipLaunchKernelGGL(tgrid_bwd_runs_kernel<true>, dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, segs, run);
-      SNERF_LAUNCH_CHECK("tgrid_encode_bwd (runs)");
+      hipLaunchKernelGGL((tgrid_runs_kernel<BWD, true>), dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, segs, run);
+      SNERF_LAUNCH_CHECK(BWD ? "tgrid_encode_bwd (runs)" : "tgrid_encode_fwd (runs)");
       return 0;
     }
     if (a.c.mode == 0) {  // explicit points in sample order
       const int64_t threads = ((a.B + TG_RUN - 1) / TG_RUN) * 2 * a.d.C;
-      hipLaunchKernelGGL(tgrid_bwd_runs_kernel<false>, dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, 1, TG_RUN);
-      SNERF_LAUNCH_CHECK("tgrid_encode_bwd (runs, points)");
-      return 0;
-    }
-  }
-  if (!BWD && !a.dy_dx && a.d.D == 3 && a.times && !a.trow && !tgrid_runs_off()) {
-    // the forward walks the same segments.  The pair sum (__shfl_xor) needs both lanes of a (channel) pair in the same loop iteration: a pair
-    // shares its group and hence its segment, so its trip count -- whatever other groups of the wave do.
-    if (a.c.mode == 1 && a.spr == a.c.S && a.B % a.c.S == 0) {
-      const int S = a.c.S;
-      const int segs = (S + TG_RUN - 1) / TG_RUN, run = (S + segs - 1) / segs;
-      const int64_t threads = (a.B / S) * segs * 2 * a.d.C;
-      hipLaunchKernelGGL(tgrid_fwd_runs_kernel<true>, dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, segs, run);
-      SNERF_LAUNCH_CHECK("tgrid_encode_fwd (runs)");
-      return 0;
-    }
-    if (a.c.mode == 0) {
-      const int64_t threads = ((a.B + TG_RUN - 1) / TG_RUN) * 2 * a.d.C;
-      hipLaunchKernelGGL(tgrid_fwd_runs_kernel<false>, dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, 1, TG_RUN);
-      SNERF_LAUNCH_CHECK("tgrid_encode_fwd (runs, points)");
+      hipLaunchKernelGGL((tgrid_runs_kernel<BWD, false>), dim3((unsigned)ceil_div(threads, 256), n_lv), dim3(256), 0, st, a, 1, TG_RUN);
+      SNERF_LAUNCH_CHECK(BWD ? "tgrid_encode_bwd (runs, points)" : "tgrid_encode_fwd (runs, points)");
       return 0;
     }
   }

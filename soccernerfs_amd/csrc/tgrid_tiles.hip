@@ -4,7 +4,7 @@
 // live column) followed by torch.optim.Adam over the dense table (NS/configs/method_configs.py:648-657) and, in between, the temporal-TV gradient of two
 // columns (NS/field_components/temporal_grid.py:352-376).
 //
-// Why: on camera rays tgrid_bwd_runs_kernel (tgrid.hip) already runs AT the chip-wide rate of memory-side float atomics -- 22 M 64-B atomic requests of
+// Why: on camera rays tgrid_runs_kernel<true> (tgrid.hip) already runs AT the chip-wide rate of memory-side float atomics -- 22 M 64-B atomic requests of
 // 12 useful bytes each in 1.26 ms for config 4's main grid (profiles/r06_tgrid_levels.json) -- and above the coarsest levels no two samples share a cell
 // (196 608 samples -> 196 5xx distinct cells per level from level 11 on), so combining across rays cannot remove requests.  What can go is the atomic
 // itself: every table row gets ONE owner.
@@ -50,14 +50,14 @@ struct TgTiles {
   TileArgs a;
   __host__ __device__ int levels() const { return a.d.L; }
   __host__ __device__ int row_floats() const { return a.d.grid_C; }
-  __device__ __forceinline__ TableLevel level(int l) const { return tg_level(a.d, l); }
+  __device__ __forceinline__ TableLevel level(int l) const { return tg_level(a.d, l, 3); }
 
   __device__ __forceinline__ bool cell(const TableLevel& lv, int l, int64_t b, uint32_t pg[3], float fr[3]) const {
     const float4 ps = a.pos4[b];
     const float x[3] = {ps.x, ps.y, ps.z};
     if ((x[0] < 0.f) || (x[0] > 1.f) || (x[1] < 0.f) || (x[1] > 1.f) || (x[2] < 0.f) || (x[2] > 1.f)) return false;  // .cu:119-124
     if (tile_gradient_is_zero<C>(a, a.d.L, l, b)) return false;
-    tg_cell(lv, a.d.align_corners != 0, x, pg, fr);
+    tg_cell(lv, a.d.align_corners != 0, x, 3, pg, fr);
     return true;
   }
 
@@ -77,7 +77,7 @@ struct TgTiles {
   };
   __device__ __forceinline__ Sample sample(const Rec& rc, const TableLevel& lv, int l, uint32_t pg[3], float fr[3]) const {
     const float x[3] = {rc.ps.x, rc.ps.y, rc.ps.z};
-    tg_cell(lv, a.d.align_corners != 0, x, pg, fr);
+    tg_cell(lv, a.d.align_corners != 0, x, 3, pg, fr);
     const int n_trows = a.d.grid_C - C - 1;
     const float t = rc.ps.w;
     const float tv = t * (float)(n_trows - 1);

@@ -44,8 +44,8 @@ class NerfplayerFullTrainer(NerfplayerStep):
         and the next step's proposal levels.  Same arithmetic (same bits in deterministic mode).  Readers of those tables outside forward() call
         wait_params() / synchronize() first; off by default for that reason.
         tiled_table_backward (round 6): inside train_step the newness and decomposition tables' gradient scatter, temporal-TV step and Adam sweep are ONE
-        owner-computes pass each (temporal_grid.TiledTableBackward, csrc/tgrid_tiles.hip): no float atomics on the deformed positions (tgrid_bwd_runs_kernel
-        <false> ran at the atomic rate, 2.0 ms per step) and no dense gradient for the two tables (24 instead of 32 B per parameter).  Same mathematics, float
+        owner-computes pass each (temporal_grid.TiledTableBackward, csrc/tgrid_tiles.hip): no float atomics on the deformed positions (tgrid_runs_kernel
+        <true, false> ran at the atomic rate, 2.0 ms per step) and no dense gradient for the two tables (24 instead of 32 B per parameter).  Same mathematics, float
         sums in another order.  Needs temporal_tv_weight > 0 (the preset); not with `deterministic`; backward() outside train_step keeps the atomic scatter.
         deterministic: every gradient accumulated across samples -- the temporal-grid and hash-grid table scatters, the hash grid's coordinate
         gradient (one add per level and sample), the weight gradients of all seven nets -- goes into 2^50-scaled 64-bit cells

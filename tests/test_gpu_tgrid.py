@@ -353,7 +353,7 @@ def test_interpolation_matches_reference_hash_encoding(name):
 
 @pytest.mark.parametrize("mode", ["rays", "points"])
 def test_run_length_forward_is_bit_identical_to_the_per_sample_kernel(mode):
-    """tgrid_fwd_runs_kernel (round 5: the eight corner values of the current cell stay in registers while consecutive samples of a ray remain in it)
+    """tgrid_runs_kernel<false> (round 5: the eight corner values of the current cell stay in registers while consecutive samples of a ray remain in it)
     against tgrid_kernel<false> (one gather of all corners per sample; SNERF_TGRID_RUNS=0 selects it): the same products summed in the same order, so the
     outputs must agree BIT FOR BIT -- on the preset's main grid (16 levels, hashed above level 5) with ragged segments (S = 48 -> 2 x 24, S = 37 ->
     2 x 19 / 18), rays that leave the box, and the explicit-point form the full NeRFPlayer feeds with deformed positions."""
@@ -395,3 +395,69 @@ def test_run_length_forward_is_bit_identical_to_the_per_sample_kernel(mode):
             outs.append(out)
         assert float(outs[1].abs().max()) > 0 and bool((outs[1] == 0).all(dim=1).any())  # some samples lie outside the box (all-zero rows)
         assert torch.equal(outs[0], outs[1]), float((outs[0] - outs[1]).abs().max())
+
+
+@pytest.mark.parametrize("mode", ["rays", "points"])
+def test_run_length_backward_matches_the_per_sample_kernel(mode):
+    """The run-length backward (csrc/tgrid.hip: tgrid_runs_kernel<true>) against tgrid_kernel<true> (SNERF_TGRID_RUNS=0) at the API level, on the inputs of the
+    forward test above: same encoder, ragged segments, clustered edges, rays that leave the box, times 0 and 1, plus a seeded grad_out in [-0.5, 0.5).  Both
+    scatter the same terms w * g * wt into 2^50-scaled fixed-point cells (snerf_tgrid_encode_bwd_fx: integer adds, so neither result depends on arrival
+    order); the run-length form first sums the terms of at most TG_RUN = 32 consecutive samples of one cell sequentially in float and converts once, the
+    per-sample form converts every term.  With A = the same scatter of |grad_out| (all interpolation and temporal weights are >= 0, so A is the cell's sum
+    of |terms|), per table cell
+        |G_runs - G_per_sample| <= 33 * 2^-24 * A + n_terms * 2^-50 :
+    a sequential float sum of <= 32 terms is off by at most gamma_32 ~ 32 u of the sum of their magnitudes (u = 2^-24) plus the one rounding of its own
+    conversion's input, and every fixed-point conversion rounds by at most 2^-51, once per term in the per-sample form and at most once per term in the
+    run-length form.  n_terms is bounded by 8 B: a sample adds at most its 8 corners to any one cell."""
+    import ctypes as C
+    import os
+
+    from soccernerfs_amd import _lib, ops
+    from soccernerfs_amd.temporal_grid import TemporalGridEncoder
+
+    gen = torch.Generator().manual_seed(21)
+    enc = TemporalGridEncoder(input_dim=3, temporal_dim=64, num_levels=16, level_dim=2, log2_hashmap_size=15, desired_resolution=2048).to(DEV)
+    with torch.no_grad():
+        enc.embeddings.copy_((torch.rand(enc.embeddings.shape, generator=gen) - 0.5).to(DEV))
+    L = _lib.lib()
+    for R, S in ((300, 48), (129, 37)):
+        o = ((torch.rand(R, 3, generator=gen) * 2 - 1) * 0.9).to(DEV)
+        d = torch.nn.functional.normalize(torch.rand(R, 3, generator=gen) * 2 - 1, dim=-1).to(DEV)
+        edges = torch.sort(torch.rand(R, S + 1, generator=gen) ** 3 * 1.6, dim=-1).values.to(DEV).contiguous()
+        times = torch.rand(R, generator=gen).to(DEV)
+        times[0], times[1] = 0.0, 1.0
+        B = R * S
+        if mode == "rays":
+            co, keep = ops.coords_from_rays(o, d, times, edges, [[-1.0] * 3, [1.0] * 3], False), None
+        else:
+            mid = (edges[:, :-1] + edges[:, 1:]) / 2
+            pts = (((o[:, None, :] + d[:, None, :] * mid[..., None]) + 1.0) / 2.0).reshape(B, 3).contiguous()
+            co, keep = ops.coords_from_points(pts), pts
+        gout = (torch.rand(B, enc.output_dim, generator=gen) - 0.5).to(DEV)
+
+        def scatter(runs, g):
+            """the cells as float64 on the host (exact: |cell| < 2^53 here) and as snerf_fx_to_float's float32"""
+            os.environ["SNERF_TGRID_RUNS"] = runs
+            try:
+                fx = torch.zeros(enc.embeddings.numel(), dtype=torch.int64, device=DEV)
+                _lib.check(L.snerf_tgrid_encode_bwd_fx(C.byref(enc.desc), C.byref(co), None, ops._ptr(times), S, C.c_int64(B), ops._ptr(g), ops._ptr(fx),
+                                                       ops._stream()), "tgrid_encode_bwd_fx")
+                torch.cuda.synchronize()
+            finally:
+                os.environ.pop("SNERF_TGRID_RUNS", None)
+            cells = fx.cpu()
+            assert int(cells.abs().max()) < 2 ** 53
+            f32 = torch.empty(fx.numel(), device=DEV)
+            ops.fx_to_float(fx, f32)
+            return cells.double() * 2.0 ** -50, f32.cpu()
+
+        (g_runs, f_runs), (g_ps, f_ps), (A, _) = scatter("1", gout), scatter("0", gout), scatter("0", gout.abs().contiguous())
+        assert float(g_ps.abs().max()) > 0 and float(g_runs.abs().max()) > 0 and float(f_runs.abs().max()) > 0 and float(f_ps.abs().max()) > 0
+        dead = A == 0
+        assert bool(dead.any()) and bool((g_runs[dead] == 0).all()) and bool((g_ps[dead] == 0).all())
+        bound = 33 * 2.0 ** -24 * A + 8 * B * 2.0 ** -50
+        err = (g_runs - g_ps).abs()
+        worst = int(torch.argmax(err - bound))
+        print(f"{mode} R={R} S={S}: max |G_runs - G_ps| = {float(err.max()):.3e}, worst cell err {float(err[worst]):.3e} against bound {float(bound[worst]):.3e}, "
+              f"max err / (2^-24 A) = {float((err / (2.0 ** -24 * A.clamp_min(1e-30)))[~dead].max()):.3f}")
+        assert bool((err <= bound).all()), (float(err[worst]), float(bound[worst]))

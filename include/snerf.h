@@ -1042,11 +1042,17 @@ int snerf_ist_sample(const float* cdf, int32_t H, int32_t W, const int64_t* chos
 
 /* ------------------------------------------------------------------------------------------------
  * Sorted plane-gradient scatter (same result as snerf_kplanes_gather_bwd, ~6x fewer atomic requests on training batches).
- *   1. snerf_kplanes_sort_samples : counting sort of the N samples, once per PLANE, by the Z-order (Morton) code of their texel
- *      at the finest scale -- one order serves every scale, because a coarser texel is a (nearly) aligned block of fine ones.
+ *   1. snerf_kplanes_sort_samples : sorts the N samples, once per PLANE, by the Z-order (Morton) code of their texel at the finest
+ *      scale (planes whose row axis is time: time row * width + x texel) -- one order serves every scale, because a coarser texel is
+ *      a (nearly) aligned block of fine ones.  Segment q of sorted_rec holds every sample once, in non-decreasing FULL key order; the
+ *      order among equal keys is unspecified.  Two LDS-binned levels (coarse bins of the key, then the low key bits inside a bin): the
+ *      cost follows N, not the number of texels; no global atomics, nothing to clear.
  *      Depends only on the sample coordinates -> can run on a side stream as soon as they are known.
- *      Workspace sizes (elements) from snerf_kplanes_sort_workspace: hist[hist_cells], rank[index_elems] (int32) and
- *      sorted_rec[index_elems][4] (float: sample id bits, the two normalised plane coordinates, 0)  (index_elems = n_planes * N).
+ *      Workspace sizes (elements) from snerf_kplanes_sort_workspace: hist[hist_cells] and rank[index_elems] (int32; two OPAQUE
+ *      workspaces -- hist, 16-byte aligned, holds the intermediate records and the bin counts; no content survives a call or means
+ *      anything to the caller) and sorted_rec[index_elems][4] (float: sample id bits, the two normalised plane coordinates, 0)
+ *      (index_elems = n_planes * N).  n_planes * N < 2^31; at most 2^22 sort cells per plane (finest resolution <= 2048:
+ *      8 KB of LDS counters per workgroup, the largest plan that is tested and measured); larger planes are refused with an error.
  *   2. snerf_kplanes_gradvec      : gvec[scale*n_planes+plane][N][C] = dL/d(interpolated value of that plane) per sample; elements are
  *      fp32 (gvec_bf16 = 0: exact, the parity path) or bf16 (gvec_bf16 = 1: half the bytes of the largest intermediate of the step; the
  *      scatter still accumulates in fp32).

@@ -11,12 +11,16 @@
 // the samples of any coarser texel (a ~power-of-two block of fine texels) are (almost always) contiguous too.
 //
 // Pipeline (NP plane segments, each with exactly N entries):
-//   K1 rank    : one lane per (sample, plane): key = cell(plane) + morton(x0, row0 at the finest scale);
-//                rank = atomicAdd(&hist[key], 1)   (int atomics)
-//   K2 scan    : exclusive prefix sum of hist (3 small kernels)
-//   K3 reorder : sorted_rec[scan[key] + rank] = {n, coord_a, coord_b} (sample id + its two normalised coordinates on that
-//                plane) -- a counting sort; positions depend only on the sample coordinates, so K1-K3 run on a side stream
-//                under the forward / MLP backward, and pass B never has to touch the ray buffers again
+//   S  sort    : key = morton(x0, row0 at the finest scale) (time planes: row0 * W + x0), ordered in two LDS-binned levels whose cost
+//                follows the entries, not the cells (kplanes_sort_common.hpp: SortPlan) -- no global atomics, nothing to clear:
+//     S1 count / scan / fill : one workgroup per (chunk of samples, plane) counts its samples per COARSE bin (key >> shift) in LDS and
+//                writes its row of a [chunks][bins] matrix; a scan over the chunks gives every chunk its offset inside a bin and the bins'
+//                totals; the fill pass scans its plane's totals in LDS, recomputes the keys, takes chunk-local slots from LDS and writes
+//                {n, coord_a, coord_b, key} to the bin's range
+//     S2 place   : one workgroup per coarse bin orders the bin by the low key bits with 2^shift LDS counters (count, scan, place) and
+//                writes sorted_rec = {n, coord_a, coord_b, 0} (sample id + its two normalised coordinates on that plane).
+//                Positions depend only on the sample coordinates, so the sort runs on a side stream under the forward / MLP
+//                backward, and pass B never has to touch the ray buffers again
 //   A  gradvec : sample-major, float4 per lane (like the forward gather): g_q = dL/d(interp of plane q) -> gvec[seg][n][C]
 //   B  scatter : per segment, lane groups of 2*C lanes (x-corner, channel) walk RUN consecutive SORTED entries, multiply by
 //                the bilinear weights, run-length-combine per row and flush with one 256-B atomic instruction per run.
@@ -33,7 +37,7 @@ __device__ __forceinline__ void seg_axes(int q, int& a, int& b) {
   a = A[q]; b = B[q];
 }
 
-// ---- K1 / K3: one lane per sample, loops over the segments ----
+// ---- texel coordinates shared by the sort and pass B ----
 // pixel coordinate of axis_tap (the clipped, un-normalised grid_sample coordinate); floor of it is the tap's i0
 __device__ __forceinline__ float axis_pix(float x, int size) {
   float fx = ((x + 1.f) / 2.f) * (float)(size - 1);
@@ -51,104 +55,192 @@ __device__ __forceinline__ AxisTap tap_from_pix(float fx, int size) {
   return t;
 }
 
-template <int NP, bool REORDER>
-__global__ __launch_bounds__(256) void sort_keys_kernel(snerf_coords c, SegTable st, int64_t N, int32_t* __restrict__ hist,
-                                                       int32_t* __restrict__ rank, const int32_t* __restrict__ scan, float4* __restrict__ sorted_rec) {
-  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  float p[4];
-  load_coords<NP>(c, n, p);
-  constexpr auto& A = PlanePairs<NP>::a;
-  constexpr auto& B = PlanePairs<NP>::b;
-  if (st.per_scale) {
-    for (int s = 0; s < st.n_scales; ++s) {
-      int i0[4], rs[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        rs[k] = st.res[s][k] > 0 ? st.res[s][k] : 1;
-        i0[k] = (int)floorf(axis_pix(p[k], rs[k]));  // == axis_tap(p, res).i0: the run key pass B compares
-      }
-#pragma unroll
-      for (int q = 0; q < NP; ++q) {
-        const int seg = s * NP + q;
-        const int key = st.cell_off[seg] + (st.row_major[q] ? i0[B[q]] * rs[A[q]] + i0[A[q]] : (int)morton2((uint32_t)i0[A[q]], (uint32_t)i0[B[q]]));
-        if (!REORDER) rank[(int64_t)seg * N + n] = atomicAdd(hist + key, 1);
-        else sorted_rec[scan[key] + rank[(int64_t)seg * N + n]] = make_float4(__int_as_float((int)n), p[A[q]], p[B[q]], 0.f);
-      }
-    }
-    return;
+// ---- the sort: level 1 (coarse bins), two small scans, level 2 (inside a bin) ----
+// what a workgroup needs to form plane q's keys: the axis pair, the two sort-grid resolutions, Morton or row-major
+struct PlaneKey {
+  int a, b, ra, rb, row_major;
+};
+template <int NP>
+__device__ __forceinline__ PlaneKey plane_key_of(const SegTable& st, int q) {
+  PlaneKey k;
+  k.a = pair_a<NP>(q); k.b = pair_b<NP>(q);
+  k.row_major = st.row_major[q];
+  const int fa = k.row_major ? st.fine_rm[k.a] : st.fine[k.a], fb = st.fine[k.b];
+  k.ra = fa > 0 ? fa : 1; k.rb = fb > 0 ? fb : 1;
+  return k;
+}
+// the plane's two coordinates of a sample (selects, so that p[] stays in registers)
+__device__ __forceinline__ void plane_coords(const PlaneKey& k, const float p[4], float& pa, float& pb) {
+  pa = k.a == 0 ? p[0] : (k.a == 1 ? p[1] : p[2]);
+  pb = k.b == 1 ? p[1] : (k.b == 2 ? p[2] : p[3]);
+}
+// i0 = floor(axis_pix) == axis_tap(p, res).i0: the run key pass B compares
+__device__ __forceinline__ uint32_t plane_key(const PlaneKey& k, float pa, float pb) {
+  const int ia = (int)floorf(axis_pix(pa, k.ra)), ib = (int)floorf(axis_pix(pb, k.rb));
+  return k.row_major ? (uint32_t)(ib * k.ra + ia) : morton2((uint32_t)ia, (uint32_t)ib);
+}
+
+// This lane's slot under LDS counter idx: one returning LDS add per lane -- or, where every active lane of the wave names the same counter
+// (a batch planted in one cell; the 64 samples of a ray on one time row), a single add for the wave instead of 64 serialised ones.
+__device__ __forceinline__ int lds_take(int32_t* ctr, int idx) {
+  const int first = __builtin_amdgcn_readfirstlane(idx);
+  const unsigned long long act = __ballot(1);
+  if (__ballot(idx == first) == act) {
+    const int before = __popcll(act & ((1ull << (threadIdx.x & 63)) - 1ull));
+    int base = 0;
+    if (before == 0) base = atomicAdd(ctr + first, __popcll(act));
+    return __builtin_amdgcn_readfirstlane(base) + before;  // the first active lane is the one that added
   }
-  int i0[4], i0f[4];
+  return atomicAdd(ctr + idx, 1);
+}
+
+// Exclusive prefix sums of the LDS words a[0, n), in place, starting at `start`: thread t owns words [t * per, (t + 1) * per).  Called by all SORT_NT
+// threads, with a barrier in front (a[] complete) and one behind (before anyone reads another thread's words); wsum: SORT_NT / 64 words of LDS.
+__device__ __forceinline__ void block_exclusive_scan(int32_t* a, int n, int start, int* wsum) {
+  const int per = (n + SORT_NT - 1) / SORT_NT;
+  const int c0 = (int)threadIdx.x * per, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int local = 0;
+  for (int k = 0; k < per; ++k)
+    if (c0 + k < n) local += a[c0 + k];
+  int incl = local;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    i0[k] = (int)floorf(axis_pix(p[k], st.fine[k] > 0 ? st.fine[k] : 1));
-    i0f[k] = (int)floorf(axis_pix(p[k], st.fine_rm[k] > 0 ? st.fine_rm[k] : 1));
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += t;
   }
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int key = st.cell_off[q] + (st.row_major[q] ? i0[B[q]] * st.fine_rm[A[q]] + i0f[A[q]] : (int)morton2((uint32_t)i0[A[q]], (uint32_t)i0[B[q]]));
-    if (!REORDER) {
-      rank[(int64_t)q * N + n] = atomicAdd(hist + key, 1);
-    } else {
-      // sorted record: sample id + its two normalised coordinates on this plane, so pass B never touches the ray buffers
-      sorted_rec[scan[key] + rank[(int64_t)q * N + n]] = make_float4(__int_as_float((int)n), p[A[q]], p[B[q]], 0.f);
+  if (lane == 63) wsum[w] = incl;
+  __syncthreads();
+  int run = start + incl - local;
+  for (int k = 0; k < w; ++k) run += wsum[k];
+  for (int k = 0; k < per; ++k)
+    if (c0 + k < n) {
+      const int v = a[c0 + k];
+      a[c0 + k] = run;
+      run += v;
     }
+}
+
+// Level 1, grid (chunks, planes).  FILL = false: count the chunk's samples per coarse bin, write the chunk's row of counts[chunks][bins] (every word,
+// so nothing has to be cleared).  FILL = true: the LDS counters start at the chunk's first slot of each bin -- the bin's base, an exclusive scan of
+// the plane's bin totals that every workgroup makes for itself in LDS (a plane's bins hold exactly N entries, so plane q starts at q * N: no scan
+// across planes, no kernel of its own), plus the chunk's scanned count -- and every sample's intermediate record {n, p_a, p_b, key} goes to the slot
+// it takes.  The workgroups of chunk 0 leave the bin bases in bin_base[] for level 2.
+template <int NP, bool FILL>
+__global__ __launch_bounds__(SORT_NT) void sort_bin_kernel(snerf_coords c, SegTable st, SortPlan sp, int64_t N, int32_t* __restrict__ counts,
+                                                          const int32_t* __restrict__ totals, int32_t* __restrict__ bin_base, float4* __restrict__ tmp) {
+  extern __shared__ int32_t s_sort[];
+  __shared__ int s_wsum[SORT_NT / 64];
+  const int q = (int)blockIdx.y, chunk = (int)blockIdx.x;
+  const int B0 = sp.bin0[q], nb = sp.bin0[q + 1] - B0, sh = sp.shift[q];
+  int32_t* mine = counts + (int64_t)chunk * sp.bin0[NP] + B0;
+  if (FILL) {
+    for (int i = threadIdx.x; i < nb; i += SORT_NT) s_sort[i] = totals[B0 + i];
+    __syncthreads();
+    block_exclusive_scan(s_sort, nb, (int)(q * N), s_wsum);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb; i += SORT_NT) {
+      const int base = s_sort[i];
+      s_sort[i] = base + mine[i];
+      if (chunk == 0) bin_base[B0 + i] = base;
+    }
+    if (chunk == 0 && q == NP - 1 && threadIdx.x == 0) bin_base[sp.bin0[NP]] = (int)(NP * N);
+  } else {
+    for (int i = threadIdx.x; i < nb; i += SORT_NT) s_sort[i] = 0;
+  }
+  __syncthreads();
+  const PlaneKey pk = plane_key_of<NP>(st, q);
+  const int64_t n0 = (int64_t)chunk * SORT_CHUNK;
+  const int64_t n1 = n0 + SORT_CHUNK < N ? n0 + SORT_CHUNK : N;
+  for (int64_t n = n0 + threadIdx.x; n < n1; n += SORT_NT) {
+    float p[4], pa, pb;
+    load_coords<NP>(c, n, p);
+    plane_coords(pk, p, pa, pb);
+    const uint32_t key = plane_key(pk, pa, pb);
+    const int slot = lds_take(s_sort, (int)(key >> sh));
+    if (FILL) tmp[slot] = make_float4(__int_as_float((int)n), pa, pb, __int_as_float((int)key));
+  }
+  if (!FILL) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb; i += SORT_NT) mine[i] = s_sort[i];
   }
 }
 
-// ---- K2: exclusive scan of int32 data[n] in place (block = 1024 elements) ----
-__global__ __launch_bounds__(256) void scan_block_kernel(int32_t* __restrict__ data, int64_t n, int32_t* __restrict__ block_sums) {
-  __shared__ int32_t s_part[256];
-  const int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-  int32_t v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = base + k < n ? data[base + k] : 0;
-  const int32_t tsum = v[0] + v[1] + v[2] + v[3];
-  s_part[threadIdx.x] = tsum;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele over the 256 thread sums
-    int32_t t = threadIdx.x >= off ? s_part[threadIdx.x - off] : 0;
-    __syncthreads();
-    s_part[threadIdx.x] += t;
-    __syncthreads();
+// Per bin: counts[chunk][bin] -> the chunk's offset inside the bin (exclusive prefix over the chunks); totals[bin] = the bin's entries.  A workgroup
+// takes 64 bins x 4 quarters of the chunks: a column's loads are independent of each other (a running sum with its store between the loads made
+// this the longest kernel of the sort), the quarters meet in LDS, and the second walk over the column finds it in cache.
+__global__ __launch_bounds__(256) void sort_scan_chunks_kernel(int32_t* __restrict__ counts, int n_chunks, int n_bins, int32_t* __restrict__ totals) {
+  __shared__ int s_part[4][64];
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int t = (int)blockIdx.x * 64 + lane;
+  const bool live = t < n_bins;
+  const int per = (n_chunks + 3) / 4;
+  const int c0 = g * per < n_chunks ? g * per : n_chunks, c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+  int32_t* col = counts + (live ? t : 0);
+  int sum = 0;
+  if (live) {
+#pragma unroll 8
+    for (int ch = c0; ch < c1; ++ch) sum += col[(int64_t)ch * n_bins];
   }
-  int32_t run = s_part[threadIdx.x] - tsum;  // exclusive prefix of this thread inside the block
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (base + k < n) data[base + k] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 255) block_sums[blockIdx.x] = s_part[255];
-}
-__global__ void scan_sums_kernel(int32_t* __restrict__ block_sums, int nb) {  // single workgroup, sequential over chunks of 1024
-  __shared__ int32_t s_part[1024];
-  __shared__ int32_t s_carry;
-  if (threadIdx.x == 0) s_carry = 0;
+  s_part[g][lane] = sum;
   __syncthreads();
-  for (int base = 0; base < nb; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int32_t v = i < nb ? block_sums[i] : 0;
-    s_part[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      int32_t t = threadIdx.x >= off ? s_part[threadIdx.x - off] : 0;
-      __syncthreads();
-      s_part[threadIdx.x] += t;
-      __syncthreads();
+  if (!live) return;
+  int run = 0;
+  for (int k = 0; k < g; ++k) run += s_part[k][lane];
+  if (g == 3) totals[t] = run + sum;
+  int ch = c0;
+  for (; ch + 8 <= c1; ch += 8) {  // eight loads in flight, then their stores
+    int v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = col[(int64_t)(ch + k) * n_bins];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      col[(int64_t)(ch + k) * n_bins] = run;
+      run += v[k];
     }
-    if (i < nb) block_sums[i] = s_carry + s_part[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_carry += s_part[1023];
-    __syncthreads();
+  }
+  for (; ch < c1; ++ch) {
+    const int v = col[(int64_t)ch * n_bins];
+    col[(int64_t)ch * n_bins] = run;
+    run += v;
   }
 }
-__global__ __launch_bounds__(256) void scan_add_kernel(int32_t* __restrict__ data, int64_t n, const int32_t* __restrict__ block_sums) {
-  const int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-  const int32_t add = block_sums[blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (base + k < n) data[base + k] += add;
+
+
+// Level 2, one workgroup per coarse bin: a counting sort of the bin's intermediate records by the low `shift` key bits.  LDS holds the 2^shift
+// counters only; the bin's range [bin_base[bin], bin_base[bin + 1]) is walked twice (count, place), however long it is.  Writes the final record
+// {n, p_a, p_b, 0}.
+__global__ __launch_bounds__(SORT_NT) void sort_place_kernel(SortPlan sp, const int32_t* __restrict__ bin_base, const float4* __restrict__ tmp,
+                                                            float4* __restrict__ sorted_rec) {
+  extern __shared__ int32_t s_sort[];
+  __shared__ int s_wsum[SORT_NT / 64];
+  const int bin = (int)blockIdx.x;
+  const int beg = bin_base[bin], end = bin_base[bin + 1];
+  if (beg == end) return;  // most bins of a real batch
+  int q = 0;
+  while (bin >= sp.bin0[q + 1]) ++q;
+  const int sh = sp.shift[q], nc = 1 << sh;
+  const uint32_t mask = (uint32_t)nc - 1u;
+  if (sh == 0 || end - beg == 1) {  // one cell per bin, or one entry: level 1 has ordered it
+    for (int i = beg + (int)threadIdx.x; i < end; i += SORT_NT) {
+      const float4 r = tmp[i];
+      sorted_rec[i] = make_float4(r.x, r.y, r.z, 0.f);
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < nc; i += SORT_NT) s_sort[i] = 0;
+  __syncthreads();
+#pragma unroll 4
+  for (int i = beg + (int)threadIdx.x; i < end; i += SORT_NT) atomicAdd(&s_sort[(uint32_t)__float_as_int(tmp[i].w) & mask], 1);
+  __syncthreads();
+  block_exclusive_scan(s_sort, nc, beg, s_wsum);
+  __syncthreads();
+  for (int i = beg + (int)threadIdx.x; i < end; i += SORT_NT) {
+    const float4 r = tmp[i];
+    const int slot = lds_take(s_sort, (int)((uint32_t)__float_as_int(r.w) & mask));
+    sorted_rec[slot] = make_float4(r.x, r.y, r.z, 0.f);
+  }
 }
+
 
 // gvec rows are fp32 (exact: the parity path) or bf16 (half the 2 GB round trip between pass A and pass B; the scatter still accumulates
 // in fp32, each contribution carries a 2^-9 relative rounding)
@@ -784,9 +876,27 @@ extern "C" int snerf_kplanes_sort_workspace(const snerf_kplanes_desc* desc, int6
   SegTable st;
   int rc = build_segs(desc, st);
   if (rc) return rc;
-  // hist: cells + room for the scan's block sums (one per 1024 cells, +1024 slack)
-  *hist_cells = (int64_t)st.cell_off[st.n_segs] + ((int64_t)st.cell_off[st.n_segs] + 1023) / 1024 + 1024;
-  *index_elems = (int64_t)st.n_segs * N;
+  SortPlan sp;
+  rc = sort_plan_make(st, N, sp);
+  if (rc) return rc;
+  *hist_cells = sp.total;  // intermediate records + count matrix + bin bases
+  *index_elems = (int64_t)st.n_planes * N;
+  return 0;
+}
+
+template <int NP>
+static int launch_sort(const snerf_coords& c, const SegTable& st, const SortPlan& sp, int64_t N, int32_t* ws, float4* sorted_n, hipStream_t s) {
+  float4* tmp = reinterpret_cast<float4*>(ws + sp.tmp_off);
+  int32_t* counts = ws + sp.counts_off;
+  int32_t* totals = ws + sp.totals_off;
+  int32_t* bin_base = ws + sp.base_off;
+  const int n_bins = sp.bin0[NP];
+  const dim3 grid((unsigned)sp.n_chunks, (unsigned)NP);
+  hipLaunchKernelGGL((sort_bin_kernel<NP, false>), grid, dim3(SORT_NT), (size_t)sp.lds1, s, c, st, sp, N, counts, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(sort_scan_chunks_kernel, dim3((unsigned)ceil_div(n_bins, 64)), dim3(256), 0, s, counts, sp.n_chunks, n_bins, totals);
+  hipLaunchKernelGGL((sort_bin_kernel<NP, true>), grid, dim3(SORT_NT), (size_t)sp.lds1, s, c, st, sp, N, counts, totals, bin_base, tmp);
+  hipLaunchKernelGGL(sort_place_kernel, dim3((unsigned)n_bins), dim3(SORT_NT), (size_t)sp.lds2, s, sp, bin_base, tmp, sorted_n);
+  SNERF_LAUNCH_CHECK("kplanes_sort_samples");
   return 0;
 }
 
@@ -800,22 +910,13 @@ extern "C" int snerf_kplanes_sort_samples(const snerf_kplanes_desc* desc, const 
   SegTable st;
   rc = build_segs(desc, st);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t cells = st.cell_off[st.n_segs];
-  const int nb = (int)((cells + 1023) / 1024);
-  int32_t* block_sums = hist + cells;
-  rc = check_hip(hipMemsetAsync(hist, 0, (size_t)cells * sizeof(int32_t), s), "kplanes_sort memset");
+  SortPlan sp;
+  rc = sort_plan_make(st, N, sp);
   if (rc) return rc;
-  const dim3 gs((unsigned)ceil_div(N, 256));
-  if (desc->n_coords == 4) hipLaunchKernelGGL((sort_keys_kernel<6, false>), gs, dim3(256), 0, s, *coords, st, N, hist, rank, nullptr, nullptr);
-  else hipLaunchKernelGGL((sort_keys_kernel<3, false>), gs, dim3(256), 0, s, *coords, st, N, hist, rank, nullptr, nullptr);
-  hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, s, hist, cells, block_sums);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, nb);
-  hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(256), 0, s, hist, cells, block_sums);
-  if (desc->n_coords == 4) hipLaunchKernelGGL((sort_keys_kernel<6, true>), gs, dim3(256), 0, s, *coords, st, N, nullptr, rank, hist, sorted_n);
-  else hipLaunchKernelGGL((sort_keys_kernel<3, true>), gs, dim3(256), 0, s, *coords, st, N, nullptr, rank, hist, sorted_n);
-  SNERF_LAUNCH_CHECK("kplanes_sort_samples");
-  return 0;
+  SNERF_REQUIRE((reinterpret_cast<uintptr_t>(hist) & 15) == 0, "kplanes_sort_samples: the workspace must be 16-byte aligned");
+  (void)rank;  // the second workspace: sized by the contract (index_elems), not needed by this sort
+  if (desc->n_coords == 4) return launch_sort<6>(*coords, st, sp, N, hist, sorted_n, (hipStream_t)stream);
+  return launch_sort<3>(*coords, st, sp, N, hist, sorted_n, (hipStream_t)stream);
 }
 
 template <int C, int NP>

@@ -34,8 +34,26 @@ def ray_like_points(R, S, dev, lo=-1.0, hi=1.0):
     return torch.cat([p, tm], -1).reshape(-1, 4).contiguous()
 
 
+def bench_sort(dev, R=4096, S=64, n_times=34):
+    """The sample sort alone (snerf_kplanes_sort_samples) at the k-planes preset's shape -- 262 144 ray-like points whose rays share ~34 distinct
+    times, as a batch drawn from a few dozen frames does -- for the preset's five scales (finest 1024^2) and config 3's six (finest 2048^2)."""
+    pts = ray_like_points(R, S, dev).view(R, S, 4).clone()
+    tv = torch.rand(n_times, device=dev) * 2 - 1
+    pts[:, :, 3] = tv[torch.randint(0, n_times, (R,), device=dev)][:, None]
+    pts = pts.view(-1, 4).contiguous()
+    co = ops.coords_from_points(pts)
+    for name, ms in (("preset, scales 1-16", (1, 2, 4, 8, 16)), ("config 3, scales 1-32", (1, 2, 4, 8, 16, 32))):
+        # C = 8, the smallest the scatter takes: the sort reads the resolutions only, and a 32-channel config-3 plane set would be 2 GB for nothing
+        ps = PlaneSet(8, [[64 * m] * 3 + [100] for m in ms], concat=True, device=dev)
+        ss = ops.SortedScatter(ps, pts.shape[0], dev)
+        ms_sort = timeit(lambda: ss.sort(co), iters=50, warm=5)
+        print(f"sample sort alone, {name}: N = {pts.shape[0]}, {ms_sort * 1e3:.1f} us ({ss.hist.numel() * 4 / 1e6:.1f} MB workspace)")
+
+
 def main():
     dev = torch.device("cuda:0")
+    if "--sort" in sys.argv[1:]:  # the sort alone, nothing else
+        return bench_sort(dev)
     R = 4096
     res = {}
     # main field: 5 scales, C=32

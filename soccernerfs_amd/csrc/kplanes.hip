@@ -89,13 +89,11 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_kernel(snerf_kplanes_d
   const int out_w = d.concat ? C * d.n_scales : C;
 
   for (int s = 0; s < d.n_scales; ++s) {
-    int pend_key[NP][2];
-    float pend_val[NP][2];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      pend_key[q][0] = pend_key[q][1] = -1;
-      pend_val[q][0] = pend_val[q][1] = 0.f;
-    }
+    PendingRun pend[NP][2];  // per plane: rows y0 and y0 + 1 of this lane's x-corner; key = the texel (row, x0) of the plane
+    const auto flush = [&](int q) {
+      const int64_t gbase = d.off[s][q] + li;
+      return [&, gbase](int key, float val) { grad_add<FX>(gplanes, gplanes_fx, gbase + (int64_t)key * C, val); };
+    };
     int res[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) res[k] = d.res[s][k] > 0 ? d.res[s][k] : 1;
@@ -151,40 +149,23 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_kernel(snerf_kplanes_d
           float part = wx[q] * (ty.w0 * ta[u][q] + ty.w1 * tb[u][q]);
           v[q] = part + xor_lanes<C>(part);
         }
-        float suf[NP + 1];
-        suf[NP] = 1.f;
-#pragma unroll
-        for (int q = NP - 1; q >= 0; --q) suf[q] = suf[q + 1] * v[q];
-        float pre = gup[u];
+        float term[NP];
+        leave_one_out<NP>(gup[u], v, term);
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-          const float gq = pre * suf[q + 1] * wx[q];
-          pre *= v[q];
+          const float gq = term[q] * wx[q];
           const AxisTap& tx = tap[u][pair_a<NP>(q)];
           const AxisTap& ty = tap[u][pair_b<NP>(q)];
           const int W = res[pair_a<NP>(q)];
-          const int64_t gbase = d.off[s][q] + li;
-#pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            const int key = (r ? ty.i1 : ty.i0) * W + tx.i0;
-            const float val = gq * (r ? ty.w1 : ty.w0);
-            if (key != pend_key[q][r]) {
-              if (pend_val[q][r] != 0.f) grad_add<FX>(gplanes, gplanes_fx, gbase + (int64_t)pend_key[q][r] * C, pend_val[q][r]);
-              pend_key[q][r] = key;
-              pend_val[q][r] = val;
-            } else {
-              pend_val[q][r] += val;
-            }
-          }
+          pend[q][0].add(ty.i0 * W + tx.i0, gq * ty.w0, flush(q));
+          pend[q][1].add(ty.i1 * W + tx.i0, gq * ty.w1, flush(q));
         }
       }
     }
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      const int64_t gbase = d.off[s][q] + li;
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-        if (pend_val[q][r] != 0.f) grad_add<FX>(gplanes, gplanes_fx, gbase + (int64_t)pend_key[q][r] * C, pend_val[q][r]);
+      pend[q][0].drain(flush(q));
+      pend[q][1].drain(flush(q));
     }
   }
 }
@@ -234,19 +215,6 @@ static int launch_bwd(const snerf_kplanes_desc* d, const float* planes, const sn
 }  // namespace snerf
 
 using namespace snerf;
-
-#define DISPATCH_C_NP(FN, ...)                                                          \
-  do {                                                                                  \
-    if (desc->n_coords == 4) {                                                          \
-      if (desc->C == 32) return FN<32, 6>(__VA_ARGS__);                                 \
-      if (desc->C == 16) return FN<16, 6>(__VA_ARGS__);                                 \
-      return FN<8, 6>(__VA_ARGS__);                                                     \
-    } else {                                                                            \
-      if (desc->C == 32) return FN<32, 3>(__VA_ARGS__);                                 \
-      if (desc->C == 16) return FN<16, 3>(__VA_ARGS__);                                 \
-      return FN<8, 3>(__VA_ARGS__);                                                     \
-    }                                                                                   \
-  } while (0)
 
 extern "C" int snerf_kplanes_gather_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
                                         float* out, snerf_stream_t stream) {

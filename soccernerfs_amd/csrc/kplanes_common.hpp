@@ -1,4 +1,4 @@
-// Device helpers shared by the K-Planes kernels (kplanes.hip, kplanes_sorted.hip).
+// Device helpers shared by the K-Planes kernels (kplanes.hip, kplanes_sorted.hip, kplanes_coords.hip and the fused field / proposal kernels).
 #pragma once
 #include "common.hpp"
 
@@ -11,9 +11,13 @@ struct AxisTap {
 
 // ATen grid_sampler semantics for align_corners=True + padding_mode="border":
 //   x_pix = ((x + 1) / 2) * (size - 1), clipped to [0, size-1]; taps floor / floor+1.
-__device__ __forceinline__ AxisTap axis_tap(float x, int size) {
+// axis_pix is that pixel coordinate and axis_tap is built from it, so floor(axis_pix(x, size)) == axis_tap(x, size).i0 by construction: the
+// sort keys and pass B's chunk-local sort words (kplanes_sorted.hip) take the floor alone and must name the cell that pass B's taps address.
+__device__ __forceinline__ float axis_pix(float x, int size) {
   float fx = ((x + 1.f) / 2.f) * (float)(size - 1);
-  fx = fminf((float)(size - 1), fmaxf(fx, 0.f));
+  return fminf((float)(size - 1), fmaxf(fx, 0.f));
+}
+__device__ __forceinline__ AxisTap tap_from_pix(float fx, int size) {
   float f0 = floorf(fx);
   AxisTap t;
   t.i0 = (int)f0;
@@ -24,6 +28,7 @@ __device__ __forceinline__ AxisTap axis_tap(float x, int size) {
   if (!in) t.w1 = 0.f;  // out-of-range corner contributes nothing (ATen within_bounds_2d)
   return t;
 }
+__device__ __forceinline__ AxisTap axis_tap(float x, int size) { return tap_from_pix(axis_pix(x, size), size); }
 
 // coordinate of sample s of ray r (snerf_coords mode 1: positions derived from rays + euclidean bin edges)
 __device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r, int s, float p[4]) {
@@ -108,5 +113,64 @@ __device__ __forceinline__ float4 plane_sample(const float* __restrict__ base, i
                      bilerp4(nw.z, ne.z, sw.z, se.z, w.x, w.y, w.z, w.w), bilerp4(nw.w, ne.w, sw.w, se.w, w.x, w.y, w.z, w.w));
 }
 
+// ---- the product rule and the run-length combiner, shared by every plane-gradient kernel ----
+__device__ __forceinline__ float loo_mul(float a, float b) { return a * b; }
+__device__ __forceinline__ float4 loo_mul(float4 a, float4 b) { return f4_mul(a, b); }
+
+// Leave-one-out products of the Hadamard product over the planes: term[q] = g * prod_{p != q} v[p], the gradient with respect to plane q's
+// interpolated value, for T = float (one channel) or float4 (four).  ONE fixed order for every kernel -- the planes in front are folded into
+// g from the left (pre), the planes behind come as a suffix product built from the right:
+//   pre = g;  term[q] = pre * suf[q + 1];  pre *= v[q]      with suf[q] = v[q] * suf[q + 1], suf[NP] = 1 (never multiplied: x * 1 is x).
+// The quotient form divides g * prod_p v[p] by v[q] and its fix-up adds these very terms, so all of them have to round alike.
+template <int NP, typename T>
+__device__ __forceinline__ void leave_one_out(T g, const T (&v)[NP], T (&term)[NP]) {
+  T suf[NP];
+  suf[NP - 1] = v[NP - 1];
+#pragma unroll
+  for (int q = NP - 2; q >= 0; --q) suf[q] = loo_mul(suf[q + 1], v[q]);
+  T pre = g;
+#pragma unroll
+  for (int q = 0; q < NP - 1; ++q) {
+    term[q] = loo_mul(pre, suf[q + 1]);
+    pre = loo_mul(pre, v[q]);
+  }
+  term[NP - 1] = pre;
+}
+
+// One pending run of a run-length combiner: contributions to the same key (a texel, in the caller's numbering) are summed in a register and
+// sent -- flush(key, sum): the caller's address arithmetic and its atomicAdd or grad_add<FX> -- only when the key changes, and once more by
+// drain() at the end of the walk.  A sum of exactly zero (a clamped tap's weight, no contribution yet) is never sent.
+struct PendingRun {
+  int key = -1;
+  float val = 0.f;
+  template <typename F>
+  __device__ __forceinline__ void add(int k, float v, F&& flush) {
+    if (k != key) {
+      drain(flush);
+      key = k;
+      val = v;
+    } else {
+      val += v;
+    }
+  }
+  template <typename F>
+  __device__ __forceinline__ void drain(F&& flush) const {
+    if (val != 0.f) flush(key, val);
+  }
+};
 
 }  // namespace snerf
+
+// the launcher FN<C, NP> of a descriptor `desc`: C = 8, 16, 32 channels, NP = 6 planes (x, y, z, t) or 3 (static scene)
+#define DISPATCH_C_NP(FN, ...)                                                          \
+  do {                                                                                  \
+    if (desc->n_coords == 4) {                                                          \
+      if (desc->C == 32) return FN<32, 6>(__VA_ARGS__);                                 \
+      if (desc->C == 16) return FN<16, 6>(__VA_ARGS__);                                 \
+      return FN<8, 6>(__VA_ARGS__);                                                     \
+    } else {                                                                            \
+      if (desc->C == 32) return FN<32, 3>(__VA_ARGS__);                                 \
+      if (desc->C == 16) return FN<16, 3>(__VA_ARGS__);                                 \
+      return FN<8, 3>(__VA_ARGS__);                                                     \
+    }                                                                                   \
+  } while (0)

@@ -101,18 +101,13 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kp
 #pragma unroll
         for (int q = 0; q < NP; ++q)
           plane_sample_slopes<C>(planes + d.off[s][q], d.res[s][pair_a<NP>(q)], tap[pair_a<NP>(q)], tap[pair_b<NP>(q)], cg, v[q], da[q], db[q]);
-        float4 suf[NP + 1];
-        suf[NP] = make_float4(1.f, 1.f, 1.f, 1.f);
-#pragma unroll
-        for (int q = NP - 1; q >= 0; --q) suf[q] = f4_mul(suf[q + 1], v[q]);
-        float4 pre = *reinterpret_cast<const float4*>(grow + (d.concat ? s * C : 0));  // upstream gradient times the planes in front
+        float4 others[NP];  // upstream gradient times every plane but q
+        leave_one_out<NP>(*reinterpret_cast<const float4*>(grow + (d.concat ? s * C : 0)), v, others);
         float acc[4] = {0.f, 0.f, 0.f, 0.f};  // in texels
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-          const float4 others = f4_mul(pre, suf[q + 1]);
-          acc[pair_a<NP>(q)] += dot4(others, da[q]);
-          acc[pair_b<NP>(q)] += dot4(others, db[q]);
-          pre = f4_mul(pre, v[q]);
+          acc[pair_a<NP>(q)] += dot4(others[q], da[q]);
+          acc[pair_b<NP>(q)] += dot4(others[q], db[q]);
         }
 #pragma unroll
         for (int k = 0; k < NC; ++k) gp[k] += acc[k] * slope[k];
@@ -188,15 +183,5 @@ extern "C" int snerf_kplanes_gather_bwd_coords(const snerf_kplanes_desc* desc, c
   SNERF_REQUIRE(grad_pts || grad_origins || grad_dirs, "kplanes_gather_bwd_coords: no output requested");
   if (N == 0) return 0;
   SNERF_REQUIRE(planes && grad_out, "kplanes_gather_bwd_coords: null buffer");
-  {
-    hipStream_t st = (hipStream_t)stream;
-    if (desc->n_coords == 4) {
-      if (desc->C == 32) return launch_bwd_coords<32, 6>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-      if (desc->C == 16) return launch_bwd_coords<16, 6>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-      return launch_bwd_coords<8, 6>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-    }
-    if (desc->C == 32) return launch_bwd_coords<32, 3>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-    if (desc->C == 16) return launch_bwd_coords<16, 3>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-    return launch_bwd_coords<8, 3>(desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, st);
-  }
+  DISPATCH_C_NP(launch_bwd_coords, desc, planes, coords, N, grad_out, grad_pts, grad_origins, grad_dirs, (hipStream_t)stream);
 }

@@ -32,7 +32,6 @@ __device__ __forceinline__ uint32_t morton2(uint32_t x, uint32_t y) { return par
 
 inline int build_segs(const snerf_kplanes_desc* d, SegTable& st) {
   const int NP = d->n_coords == 4 ? 6 : 3;
-  static const int PA6[6] = {0, 0, 0, 1, 1, 2}, PB6[6] = {1, 2, 3, 2, 3, 3}, PA3[3] = {0, 0, 1}, PB3[3] = {1, 2, 2};
   st.n_planes = NP;
   for (int k = 0; k < 4; ++k) {
     int fine = 1;
@@ -48,7 +47,7 @@ inline int build_segs(const snerf_kplanes_desc* d, SegTable& st) {
   st.per_scale = 0;
   for (int q = 0; q < 6; ++q) st.row_major[q] = 0, st.cells[q] = 1;
   for (int q = 0; q < NP; ++q) {
-    const int a = NP == 6 ? PA6[q] : PA3[q], b = NP == 6 ? PB6[q] : PB3[q];
+    const int a = NP == 6 ? pair_a<6>(q) : pair_a<3>(q), b = NP == 6 ? pair_b<6>(q) : pair_b<3>(q);
     // planes whose row axis is time: time is not multiscale, so (time row, fine x) row-major keeps every scale's runs whole
     st.row_major[q] = (NP == 6 && b == 3) ? 1 : 0;
     int64_t cells;

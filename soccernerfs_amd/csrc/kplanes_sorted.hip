@@ -30,31 +30,6 @@
 
 namespace snerf {
 
-template <int NP>
-__device__ __forceinline__ void seg_axes(int q, int& a, int& b) {
-  constexpr auto& A = PlanePairs<NP>::a;
-  constexpr auto& B = PlanePairs<NP>::b;
-  a = A[q]; b = B[q];
-}
-
-// ---- texel coordinates shared by the sort and pass B ----
-// pixel coordinate of axis_tap (the clipped, un-normalised grid_sample coordinate); floor of it is the tap's i0
-__device__ __forceinline__ float axis_pix(float x, int size) {
-  float fx = ((x + 1.f) / 2.f) * (float)(size - 1);
-  return fminf((float)(size - 1), fmaxf(fx, 0.f));
-}
-__device__ __forceinline__ AxisTap tap_from_pix(float fx, int size) {
-  float f0 = floorf(fx);
-  AxisTap t;
-  t.i0 = (int)f0;
-  t.w0 = (f0 + 1.f) - fx;
-  t.w1 = fx - f0;
-  bool in = (t.i0 + 1) <= (size - 1);
-  t.i1 = in ? t.i0 + 1 : t.i0;
-  if (!in) t.w1 = 0.f;
-  return t;
-}
-
 // ---- the sort: level 1 (coarse bins), two small scans, level 2 (inside a bin) ----
 // what a workgroup needs to form plane q's keys: the axis pair, the two sort-grid resolutions, Morton or row-major
 struct PlaneKey {
@@ -74,7 +49,7 @@ __device__ __forceinline__ void plane_coords(const PlaneKey& k, const float p[4]
   pa = k.a == 0 ? p[0] : (k.a == 1 ? p[1] : p[2]);
   pb = k.b == 1 ? p[1] : (k.b == 2 ? p[2] : p[3]);
 }
-// i0 = floor(axis_pix) == axis_tap(p, res).i0: the run key pass B compares
+// the sample's cell on the sort grid (floor of axis_pix: kplanes_common.hpp)
 __device__ __forceinline__ uint32_t plane_key(const PlaneKey& k, float pa, float pb) {
   const int ia = (int)floorf(axis_pix(pa, k.ra)), ib = (int)floorf(axis_pix(pb, k.rb));
   return k.row_major ? (uint32_t)(ib * k.ra + ia) : morton2((uint32_t)ia, (uint32_t)ib);
@@ -275,19 +250,38 @@ __global__ __launch_bounds__(256) void gradvec_kernel(snerf_kplanes_desc d, cons
     float4 v[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) v[q] = plane_sample<C>(planes + d.off[s][q], d.res[s][A[q]], tap[A[q]], tap[B[q]], cg);
-    const float4 g = *reinterpret_cast<const float4*>(grow + (d.concat ? s * C : 0));
-    float4 suf[NP + 1];
-    suf[NP] = make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 gq[NP];
+    leave_one_out<NP>(*reinterpret_cast<const float4*>(grow + (d.concat ? s * C : 0)), v, gq);
 #pragma unroll
-    for (int q = NP - 1; q >= 0; --q) suf[q] = f4_mul(suf[q + 1], v[q]);
-    float4 pre = g;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const float4 gq = f4_mul(pre, suf[q + 1]);
-      pre = f4_mul(pre, v[q]);
-      store_gq(gvec, ((int64_t)(s * NP + q) * N + n) * C + cg * 4, gq);
-    }
+    for (int q = 0; q < NP; ++q) store_gq(gvec, ((int64_t)(s * NP + q) * N + n) * C + cg * 4, gq[q]);
   }
+}
+
+// ---- pass B: what a lane group works on ----
+// Lane group `group` of a launch that starts at segment seg_begin takes `len` consecutive sorted entries, [i0, i0 + cnt), of segment seg = (scale s,
+// plane q): a W x H plane whose sorted records of these entries start at rec (the plane's order is shared by all scales unless per_scale).
+struct PassBSeg {
+  int seg, s, q, W, H, cnt;
+  int64_t i0;
+  const float4* rec;
+};
+// false: the group lies beyond the last segment (d ends at the launch's last scale) or beyond the last entry and has nothing to do
+template <int NP>
+__device__ __forceinline__ bool passb_segment(const snerf_kplanes_desc& d, int64_t N, const float4* __restrict__ sorted_rec, int64_t group,
+                                              int64_t groups_per_seg, int seg_begin, int per_scale, int len, PassBSeg& g) {
+  g.seg = seg_begin + (int)(group / groups_per_seg);
+  if (g.seg >= d.n_scales * NP) return false;
+  g.i0 = (group - (int64_t)(g.seg - seg_begin) * groups_per_seg) * len;
+  if (g.i0 >= N) return false;
+  g.cnt = (int)((N - g.i0) < len ? (N - g.i0) : len);
+  g.s = g.seg / NP;
+  g.q = g.seg % NP;
+  constexpr auto& A = PlanePairs<NP>::a;
+  constexpr auto& B = PlanePairs<NP>::b;
+  g.W = d.res[g.s][A[g.q]];
+  g.H = d.res[g.s][B[g.q]] > 0 ? d.res[g.s][B[g.q]] : 1;
+  g.rec = sorted_rec + (int64_t)(per_scale ? g.seg : g.q) * N + g.i0;
+  return true;
 }
 
 // ---- pass B: sorted run-length scatter ----
@@ -305,20 +299,14 @@ __global__ __launch_bounds__(256) void scatter_sorted_kernel(snerf_kplanes_desc 
   const int64_t group = LPS == 64 ? (int64_t)blockIdx.x * (blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : gid / LPS;
   const int li = (int)(gid % LPS);
   const int half = li / C, ch = li % C;
-  const int seg = seg_begin + (int)(group / groups_per_seg);
-  if (seg >= d.n_scales * NP) return;
-  const int64_t i0 = (group - (int64_t)(seg - seg_begin) * groups_per_seg) * run;
-  if (i0 >= N) return;
-  const int cnt = (int)((N - i0) < run ? (N - i0) : run);
-  const int s = seg / NP, q = seg % NP;
-  int a, b;
-  seg_axes<NP>(q, a, b);
-  const int W = d.res[s][a], H = d.res[s][b] > 0 ? d.res[s][b] : 1;
-  const float4* rec = sorted_rec + (int64_t)(per_scale ? seg : q) * N + i0;  // the plane's order is shared by all scales unless per_scale
-  const GV* gv = gvec + (int64_t)seg * N * C + ch;
-  float* gbase = gplanes + d.off[s][q] + li;
-  int pend_key[2] = {-1, -1};
-  float pend_val[2] = {0.f, 0.f};
+  PassBSeg sg;
+  if (!passb_segment<NP>(d, N, sorted_rec, group, groups_per_seg, seg_begin, per_scale, run, sg)) return;
+  const int cnt = sg.cnt, W = sg.W, H = sg.H;
+  const float4* rec = sg.rec;
+  const GV* gv = gvec + (int64_t)sg.seg * N * C + ch;
+  float* gbase = gplanes + d.off[sg.s][sg.q] + li;
+  PendingRun pend[2];  // rows y0 and y0 + 1 of this lane's x-corner; key = the texel (row, x0)
+  const auto flush = [&](int key, float val) { atomicAdd(gbase + (int64_t)key * C, val); };
   if (LPS == 64) {
     // The per-entry work (two bilinear taps, keys) is the same for all 64 lanes: do it LANE-PARALLEL for 64 entries at a time
     // (lane l handles entry base + l), then walk the 64 entries in order broadcasting the precomputed values with
@@ -352,16 +340,7 @@ __global__ __launch_bounds__(256) void scatter_sorted_kernel(snerf_kplanes_desc 
             const float wy[2] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wya), uu)),
                                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wyb), uu))};
 #pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-              const float val = gx * wy[rr];
-              if (key[rr] != pend_key[rr]) {
-                if (pend_val[rr] != 0.f) atomicAdd(gbase + (int64_t)pend_key[rr] * C, pend_val[rr]);
-                pend_key[rr] = key[rr];
-                pend_val[rr] = val;
-              } else {
-                pend_val[rr] += val;
-              }
-            }
+            for (int rr = 0; rr < 2; ++rr) pend[rr].add(key[rr], gx * wy[rr], flush);
           }
         }
       }
@@ -380,24 +359,13 @@ __global__ __launch_bounds__(256) void scatter_sorted_kernel(snerf_kplanes_desc 
         const AxisTap tx = axis_tap(r[u].y, W);
         const AxisTap ty = axis_tap(r[u].z, H);
         const float gx = g[u] * (half ? tx.w1 : tx.w0);
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-          const int key = (rr ? ty.i1 : ty.i0) * W + tx.i0;
-          const float val = gx * (rr ? ty.w1 : ty.w0);
-          if (key != pend_key[rr]) {
-            if (pend_val[rr] != 0.f) atomicAdd(gbase + (int64_t)pend_key[rr] * C, pend_val[rr]);
-            pend_key[rr] = key;
-            pend_val[rr] = val;
-          } else {
-            pend_val[rr] += val;
-          }
-        }
+        pend[0].add(ty.i0 * W + tx.i0, gx * ty.w0, flush);
+        pend[1].add(ty.i1 * W + tx.i0, gx * ty.w1, flush);
       }
     }
   }
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr)
-    if (pend_val[rr] != 0.f) atomicAdd(gbase + (int64_t)pend_key[rr] * C, pend_val[rr]);
+  pend[0].drain(flush);
+  pend[1].drain(flush);
 }
 
 // ---- pass B, C = 32: chunk-local regrouping by THIS scale's texel key, run-length combining, x-carry ----
@@ -463,6 +431,53 @@ struct BitonicK<1> {
   static __device__ __forceinline__ void run(uint32_t (&)[4], int) {}
 };
 
+// The chunk prelude of both kernels below.  The wave re-sorts ITS chunk (<= 256 entries of segment g, entry e = r * 64 + lane) by the segment's
+// own texel key and leaves one 8-dword record per entry in R (this wave's LDS), in WALK order:
+//   {hd.x, x0 | y0 << 16 (the cell: what the walk compares), hd.z, hd.w, w(x0y0), w(x0y1), w(x1y0), w(x1y1)}
+// with hd.x, hd.z, hd.w from pack(hd, sample id, tx, ty): the kernel's own offsets (elements or bytes) and flags.  Positions >= cnt hold a null
+// record: a key no cell has, zero offsets, zero weights.  Everything per-entry is prepared here lane-parallel (4 entries per lane) so that the walk --
+// one or two entries per wave instruction -- costs ~10 VALU instructions per entry: the first version spent ~60 and was VALU-issue bound.
+template <typename Pack>
+__device__ __forceinline__ void passb_chunk_records(const PassBSeg& g, int lane, uint32_t* R, Pack&& pack) {
+  const int W = g.W, H = g.H, cnt = g.cnt;
+  const bool sortable = (int64_t)W * H <= (1 << 23);  // key << 8 | index must fit 31 bits
+  // 1. sort words: (row * W + x0) << 8 | entry
+  uint32_t word[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int e = r * 64 + lane;
+    word[r] = 0xffffffffu;
+    if (e < cnt) {
+      const float4 rc = g.rec[e];
+      const int x0 = (int)floorf(axis_pix(rc.y, W)), y0 = (int)floorf(axis_pix(rc.z, H));
+      word[r] = sortable ? (((uint32_t)(y0 * W + x0) << 8) | (uint32_t)e) : (uint32_t)e;
+    }
+  }
+  // 2. in-wave bitonic sort (ascending; 0xffffffff pads go last).  Not sortable (> 2^23 texels): the words are already ascending.
+  if (sortable) BitonicK<256>::run(word, lane);
+  // 3. the records, written at their position in the sorted order
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int e = r * 64 + lane;
+    uint4 hd = make_uint4(0u, 0xffffffffu, 0u, 0u);
+    float4 wt = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (e < cnt) {
+      const float4 rc = g.rec[word[r] & 255u];
+      const AxisTap tx = axis_tap(rc.y, W);
+      const AxisTap ty = axis_tap(rc.z, H);
+      hd.y = (uint32_t)tx.i0 | ((uint32_t)ty.i0 << 16);
+      pack(hd, (uint32_t)__float_as_int(rc.x), tx, ty);
+      const float4 tw = tap_weights(tx, ty);     // (x0y0, x1y0, x0y1, x1y1): the forward's products, bit for bit
+      wt = make_float4(tw.x, tw.z, tw.y, tw.w);  // stored (x0y0, x0y1 | x1y0, x1y1): one float2 per x-corner; a clamped second tap has weight 0
+    }
+    *reinterpret_cast<uint4*>(R + e * 8) = hd;
+    *reinterpret_cast<float4*>(R + e * 8 + 4) = wt;
+  }
+  // the records were stored one lane per entry and are read back by every lane of the wave: order the LDS stores before the loads
+  // explicitly (same wave, so no s_barrier -- but neither the compiler nor the LDS queue may move a load above these stores)
+  wave_lds_publish();
+}
+
 // QUOT (the quotient form, snerf_kplanes_scatter_quotient): gvec is ONE tensor G[N][row_stride] = gfeat .* feat (feat = the forward's product
 // over the six planes), and the gradient vector of plane q at an entry is G / v_q with v_q re-interpolated here from the entry's cell --
 // the 4 texels this lane group is about to add into, so the reads follow the sorted order and stay in cache.  lane = (x-corner, channel):
@@ -474,72 +489,28 @@ __global__ __launch_bounds__(256) void scatter_grouped_kernel(snerf_kplanes_desc
                                                              int64_t groups_per_seg, int seg_begin, int per_scale,
                                                              const float* __restrict__ planes = nullptr, int row_stride = 0) {
   constexpr int C = 32, CH = 256, UNROLL = 16;
-  // per wave, per entry (in WALK order) 8 dwords: {gvec row offset (elements), x0 | y0 << 16, -, -, wx0*wy0, wx0*wy1, wx1*wy0, wx1*wy1}.
-  // Everything per-entry is prepared lane-parallel (4 entries per lane) so that the walk -- one entry per wave instruction -- costs
-  // ~10 VALU instructions per entry: the first version of this kernel spent ~60 and was VALU-issue bound (0.79 ms with 43 % fewer
-  // atomic instructions than the plain run-length kernel's 0.81 ms).
+  // per wave, per entry (in WALK order) 8 dwords: {gvec row offset (elements), x0 | y0 << 16, QUOT: texel (x0, y0) offset in the plane (elements),
+  // QUOT: x1-exists | y1-exists << 1, wx0*wy0, wx0*wy1, wx1*wy0, wx1*wy1}
   __shared__ __align__(16) uint32_t s_rec[4][CH * 8];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int half = lane >> 5, ch = lane & 31;
-  const int64_t group = (int64_t)blockIdx.x * 4 + wave;
-  const int seg = seg_begin + (int)(group / groups_per_seg);
-  if (seg >= d.n_scales * NP) return;
-  const int64_t i0 = (group - (int64_t)(seg - seg_begin) * groups_per_seg) * CH;
-  if (i0 >= N) return;
-  const int cnt = (int)((N - i0) < CH ? (N - i0) : CH);
-  const int s = seg / NP, q = seg % NP;
-  int a, b;
-  seg_axes<NP>(q, a, b);
-  const int W = d.res[s][a], H = d.res[s][b] > 0 ? d.res[s][b] : 1;
-  const float4* rec = sorted_rec + (int64_t)(per_scale ? seg : q) * N + i0;
-  // wave-uniform base; rows are addressed with 32-bit element offsets
-  const GV* gseg = QUOT ? gvec + (int64_t)s * C : gvec + (int64_t)seg * N * C;
+  PassBSeg sg;
+  if (!passb_segment<NP>(d, N, sorted_rec, (int64_t)blockIdx.x * 4 + wave, groups_per_seg, seg_begin, per_scale, CH, sg)) return;
+  const int cnt = sg.cnt, W = sg.W, s = sg.s, q = sg.q;
+  // wave-uniform base; rows are addressed with 32-bit element offsets (the launcher guarantees N * C < 2^31)
+  const GV* gseg = QUOT ? gvec + (int64_t)s * C : gvec + (int64_t)sg.seg * N * C;
   const uint32_t rstride = QUOT ? (uint32_t)row_stride : (uint32_t)C;
   float* gch = gplanes + d.off[s][q] + ch;
   const float* pch = QUOT ? planes + d.off[s][q] + ch : nullptr;
   uint32_t* R = s_rec[wave];
-  const bool sortable = (int64_t)W * H <= (1 << 23);  // key << 8 | index must fit 31 bits (the launcher guarantees N * C < 2^31)
-
-  // 1. sort words: (row * W + x0) << 8 | entry, entry e = r * 64 + lane
-  uint32_t word[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int e = r * 64 + lane;
-    word[r] = 0xffffffffu;
-    if (e < cnt) {
-      const float4 rc = rec[e];
-      const int x0 = (int)floorf(axis_pix(rc.y, W)), y0 = (int)floorf(axis_pix(rc.z, H));  // == axis_tap(.).i0
-      word[r] = sortable ? (((uint32_t)(y0 * W + x0) << 8) | (uint32_t)e) : (uint32_t)e;
+  passb_chunk_records(sg, lane, R, [&](uint4& hd, uint32_t n, const AxisTap& tx, const AxisTap& ty) {
+    hd.x = n * rstride;
+    if (QUOT) {
+      hd.z = (uint32_t)(ty.i0 * W + tx.i0) * (uint32_t)C;
+      hd.w = (tx.i1 != tx.i0 ? 1u : 0u) | (ty.i1 != ty.i0 ? 2u : 0u);
     }
-  }
-  // 2. in-wave bitonic sort (ascending; 0xffffffff pads go last).  Not sortable (> 2^23 texels): the words are already ascending.
-  if (sortable) BitonicK<CH>::run(word, lane);
-  // 3. walk records, written at their position in the sorted order; positions >= cnt get a null record (zero weights)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int e = r * 64 + lane;
-    uint4 hd = make_uint4(0u, 0xffffffffu, 0u, 0u);
-    float4 wt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (e < cnt) {
-      const float4 rc = rec[word[r] & 255u];
-      const AxisTap tx = axis_tap(rc.y, W);
-      const AxisTap ty = axis_tap(rc.z, H);
-      hd.x = (uint32_t)__float_as_int(rc.x) * rstride;
-      hd.y = (uint32_t)tx.i0 | ((uint32_t)ty.i0 << 16);
-      if (QUOT) {
-        hd.z = (uint32_t)(ty.i0 * W + tx.i0) * (uint32_t)C;
-        hd.w = (tx.i1 != tx.i0 ? 1u : 0u) | (ty.i1 != ty.i0 ? 2u : 0u);
-      }
-      const float4 tw = tap_weights(tx, ty);                  // (x0y0, x1y0, x0y1, x1y1): the forward's products, bit for bit
-      wt = make_float4(tw.x, tw.z, tw.y, tw.w);               // stored as (x0y0, x0y1 | x1y0, x1y1): one float2 per x-corner; a clamped second tap has weight 0
-    }
-    *reinterpret_cast<uint4*>(R + e * 8) = hd;
-    *reinterpret_cast<float4*>(R + e * 8 + 4) = wt;
-  }
-  // the records were stored one lane per entry and are read back by every lane of the wave: order the LDS stores before the loads
-  // explicitly (same wave, so no s_barrier -- but neither the compiler nor the LDS queue may move a load above these stores)
-  wave_lds_publish();
-  // 4. the walk.  One pending cell (x0 | y0 << 16 = ppk) with two accumulators per lane: rows y0 and y0 + 1; lane = (x-corner, channel).
+  });
+  // the walk.  One pending cell (x0 | y0 << 16 = ppk) with two accumulators per lane: rows y0 and y0 + 1; lane = (x-corner, channel).
   //    A row or column beyond the border only ever accumulates zeros and is never flushed (guards on != 0).
   uint32_t ppk = 0xfffffff0u;  // matches no record, nor record - 1
   float p0 = 0.f, p1 = 0.f;
@@ -628,59 +599,20 @@ __global__ __launch_bounds__(256) void scatter_halfwave_kernel(snerf_kplanes_des
   __shared__ __align__(16) uint32_t s_rec[4][CH * 8];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int half = lane >> 5, ch = lane & 31;
-  const int64_t group = (int64_t)blockIdx.x * 4 + wave;
-  const int seg = seg_begin + (int)(group / groups_per_seg);
-  if (seg >= d.n_scales * NP) return;
-  const int64_t i0 = (group - (int64_t)(seg - seg_begin) * groups_per_seg) * CH;
-  if (i0 >= N) return;
-  const int cnt = (int)((N - i0) < CH ? (N - i0) : CH);
-  const int s = seg / NP, q = seg % NP;
-  int a, b;
-  seg_axes<NP>(q, a, b);
-  const int W = d.res[s][a], H = d.res[s][b] > 0 ? d.res[s][b] : 1;
-  const float4* rec = sorted_rec + (int64_t)(per_scale ? seg : q) * N + i0;
-  const char* gseg = reinterpret_cast<const char*>(QUOT ? gvec + (int64_t)s * C : gvec + (int64_t)seg * N * C);
+  PassBSeg sg;
+  if (!passb_segment<NP>(d, N, sorted_rec, (int64_t)blockIdx.x * 4 + wave, groups_per_seg, seg_begin, per_scale, CH, sg)) return;
+  const int cnt = sg.cnt, W = sg.W, s = sg.s, q = sg.q;
+  const char* gseg = reinterpret_cast<const char*>(QUOT ? gvec + (int64_t)s * C : gvec + (int64_t)sg.seg * N * C);
   const uint32_t rstrideB = (QUOT ? (uint32_t)row_stride : (uint32_t)C) * 4u;
   char* gbase = reinterpret_cast<char*>(gplanes + d.off[s][q]);
   const char* pbase = QUOT ? reinterpret_cast<const char*>(planes + d.off[s][q]) : nullptr;
   uint32_t* R = s_rec[wave];
-  const bool sortable = (int64_t)W * H <= (1 << 23);
   const uint32_t rowB = (uint32_t)W * (uint32_t)(C * 4);
-
-  uint32_t word[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int e = r * 64 + lane;
-    word[r] = 0xffffffffu;
-    if (e < cnt) {
-      const float4 rc = rec[e];
-      const int x0 = (int)floorf(axis_pix(rc.y, W)), y0 = (int)floorf(axis_pix(rc.z, H));
-      word[r] = sortable ? (((uint32_t)(y0 * W + x0) << 8) | (uint32_t)e) : (uint32_t)e;
-    }
-  }
-  if (sortable) BitonicK<CH>::run(word, lane);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int e = r * 64 + lane;
-    uint4 hd = make_uint4(0u, 0xffffffffu, 0u, 0u);  // null record: zero weights, a key no cell has
-    float4 wt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (e < cnt) {
-      const float4 rc = rec[word[r] & 255u];
-      const AxisTap tx = axis_tap(rc.y, W);
-      const AxisTap ty = axis_tap(rc.z, H);
-      hd.x = (uint32_t)__float_as_int(rc.x) * rstrideB;
-      hd.y = (uint32_t)tx.i0 | ((uint32_t)ty.i0 << 16);
-      hd.z = (uint32_t)(ty.i0 * W + tx.i0) * (uint32_t)(C * 4);
-      hd.w = (tx.i1 != tx.i0 ? (uint32_t)(C * 4) : 0u) | (ty.i1 != ty.i0 ? 0x80000000u : 0u);
-      const float4 tw = tap_weights(tx, ty);     // (x0y0, x1y0, x0y1, x1y1): the forward's products, bit for bit
-      wt = make_float4(tw.x, tw.z, tw.y, tw.w);  // stored (x0y0, x0y1, x1y0, x1y1)
-    }
-    *reinterpret_cast<uint4*>(R + e * 8) = hd;
-    *reinterpret_cast<float4*>(R + e * 8 + 4) = wt;
-  }
-  // the records were stored one lane per entry and are read back by every lane of the wave: order the LDS stores before the loads
-  // explicitly (same wave, so no s_barrier -- but neither the compiler nor the LDS queue may move a load above these stores)
-  wave_lds_publish();
+  passb_chunk_records(sg, lane, R, [&](uint4& hd, uint32_t n, const AxisTap& tx, const AxisTap& ty) {
+    hd.x = n * rstrideB;
+    hd.z = (uint32_t)(ty.i0 * W + tx.i0) * (uint32_t)(C * 4);
+    hd.w = (tx.i1 != tx.i0 ? (uint32_t)(C * 4) : 0u) | (ty.i1 != ty.i0 ? 0x80000000u : 0u);
+  });
   // the walk: this half's entries are R[half * HALF + i]; pending cell = (pk, pa: byte offset of its (x0, y0) texel + this lane's channel,
   // pdx / pdy: byte steps to its x0 + 1 column / y0 + 1 row, 0 where clamped) with accumulators p00 (x0,y0), p01 (x0,y1), p10 (x1,y0), p11 (x1,y1).
   // The pending cell starts as the half's FIRST entry with empty accumulators, so no flush ever sees an invalid cell.  Zero sums (a clamped
@@ -827,21 +759,16 @@ __global__ __launch_bounds__(256) void quotient_fixup_kernel(snerf_kplanes_desc 
       zeros += fabsf(v[q]) < QUOT_TINY;
     }
     if (zeros >= 2) continue;
-    float suf[NP + 1];
-    suf[NP] = 1.f;
-#pragma unroll
-    for (int q = NP - 1; q >= 0; --q) suf[q] = suf[q + 1] * v[q];
-    float pre = g;
+    float term[NP];  // g * prod_{p != q} v_p
+    leave_one_out<NP>(g, v, term);
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      const float term = pre * suf[q + 1];  // g * prod_{p != q} v_p
-      pre *= v[q];
       if (zeros == 1 && fabsf(v[q]) >= QUOT_TINY) continue;  // one vanished plane: only IT has a non-zero gradient
       const AxisTap& tx = tap[pair_a<NP>(q)];
       const AxisTap& ty = tap[pair_b<NP>(q)];
       const int W = d.res[s][pair_a<NP>(q)];
       float* gb = gplanes + d.off[s][q] + ch;
-      const float a00 = term * tx.w0 * ty.w0, a01 = term * tx.w0 * ty.w1, a10 = term * tx.w1 * ty.w0, a11 = term * tx.w1 * ty.w1;
+      const float a00 = term[q] * tx.w0 * ty.w0, a01 = term[q] * tx.w0 * ty.w1, a10 = term[q] * tx.w1 * ty.w0, a11 = term[q] * tx.w1 * ty.w1;
       if (a00 != 0.f) atomicAdd(gb + ((int64_t)ty.i0 * W + tx.i0) * C, a00);
       if (a01 != 0.f) atomicAdd(gb + ((int64_t)ty.i1 * W + tx.i0) * C, a01);
       if (a10 != 0.f) atomicAdd(gb + ((int64_t)ty.i0 * W + tx.i1) * C, a10);
@@ -928,67 +855,60 @@ static int launch_gradvec(const snerf_kplanes_desc* d, const float* planes, cons
   SNERF_LAUNCH_CHECK("kplanes_gradvec");
   return 0;
 }
-// scatter_halfwave_kernel addresses texels and gradient rows with 32-bit BYTE offsets.  SNERF_PASSB_GROUPED=1 (dev A-B) keeps the round-2 kernel.
-static bool halfwave_ok(const snerf_kplanes_desc* d, int scale_begin, int scale_end) {
-  const char* env = getenv("SNERF_PASSB_GROUPED");  // read per call: tools/bench_passb.py flips it inside one process
-  const bool forced_off = env && atoi(env) != 0;
-  if (forced_off || d->C != 32) return false;
-  for (int s = scale_begin; s < scale_end; ++s) {
-    int64_t mx = 1;
-    for (int k = 0; k < d->n_coords; ++k) mx = mx > d->res[s][k] ? mx : d->res[s][k];
-    if (mx * mx * d->C * 4 >= (1LL << 32) || mx >= 65536) return false;
-  }
-  return true;
+// What a pass-B launch over scales [scale_begin, scale_end) needs, for both forms.  row_stride: floats between two samples' gradient rows (C for
+// the product form's per-segment vectors, C * n_scales for the quotient form's G).
+struct PassBLaunch {
+  snerf_kplanes_desc dd;  // the descriptor cut off at scale_end: the kernels stop at segment dd.n_scales * NP
+  SegTable st;
+  int64_t gps;      // lane groups per segment: one per 256 sorted entries
+  dim3 grid;        // of the two chunk kernels: 4 waves = 4 lane groups per workgroup
+  int64_t max_res;  // the largest resolution of the scales in the range
+  bool halfwave;    // scatter_halfwave_kernel may run: its 32-bit BYTE offsets reach every gradient row and every texel, x0 | y0 << 16 holds the cell
+};
+static int passb_launch_make(const snerf_kplanes_desc* d, int64_t N, int scale_begin, int scale_end, int64_t row_stride, PassBLaunch& L) {
+  L.dd = *d;
+  L.dd.n_scales = scale_end;
+  int rc = build_segs(d, L.st);
+  if (rc) return rc;
+  L.gps = (N + 255) / 256;
+  L.grid = dim3((unsigned)ceil_div(L.gps * (scale_end - scale_begin) * L.st.n_planes, 4));
+  L.max_res = 1;
+  for (int s = scale_begin; s < scale_end; ++s)
+    for (int k = 0; k < d->n_coords; ++k) L.max_res = L.max_res > d->res[s][k] ? L.max_res : d->res[s][k];
+  const char* env = getenv("SNERF_PASSB_GROUPED");  // 1 (dev A-B) keeps scatter_grouped_kernel; read per call: tools/bench_passb.py flips it inside one process
+  L.halfwave = !(env && atoi(env) != 0) && d->C == 32 && N * row_stride * 4 < (1LL << 32) && L.max_res * L.max_res * d->C * 4 < (1LL << 32) &&
+               L.max_res < 65536;
+  return 0;
 }
 
 template <int C, int NP>
 static int launch_scatter_sorted(const snerf_kplanes_desc* d, int64_t N, const void* gvec, int gvec_bf16, const float4* sorted_n, float* gp, int scale_begin,
                                  int scale_end, hipStream_t st) {
-  constexpr int run = 256;
-  const int64_t groups_per_seg = (N + run - 1) / run;
-  // the kernel stops at segment n_scales * NP: hand it a descriptor that ends at scale_end
-  snerf_kplanes_desc dd = *d;
-  dd.n_scales = scale_end;
-  SegTable stb;
-  int rc = build_segs(d, stb);
+  PassBLaunch L;
+  int rc = passb_launch_make(d, N, scale_begin, scale_end, C, L);
   if (rc) return rc;
+  const int seg0 = scale_begin * NP;
   if (C == 32 && N * C < (1LL << 31)) {  // 32-bit gvec row offsets inside the kernel
-    const int64_t gps = (N + 255) / 256;
-    const dim3 grid((unsigned)ceil_div(gps * (scale_end - scale_begin) * NP, 4));
-    if (!gvec_bf16 && N * C * 4 < (1LL << 32) && halfwave_ok(d, scale_begin, scale_end)) {
-      hipLaunchKernelGGL((scatter_halfwave_kernel<NP, false>), grid, dim3(256), 0, st, dd, N, (const float*)gvec, sorted_n, gp, gps, scale_begin * NP,
-                         stb.per_scale, nullptr, 0);
+    if (!gvec_bf16 && L.halfwave) {
+      hipLaunchKernelGGL((scatter_halfwave_kernel<NP, false>), L.grid, dim3(256), 0, st, L.dd, N, (const float*)gvec, sorted_n, gp, L.gps, seg0, L.st.per_scale,
+                         nullptr, 0);
       SNERF_LAUNCH_CHECK("kplanes_scatter_halfwave");
       return 0;
     }
-    if (gvec_bf16) hipLaunchKernelGGL((scatter_grouped_kernel<NP, __bf16>), grid, dim3(256), 0, st, dd, N, (const __bf16*)gvec, sorted_n, gp, gps,
-                                      scale_begin * NP, stb.per_scale);
-    else hipLaunchKernelGGL((scatter_grouped_kernel<NP, float>), grid, dim3(256), 0, st, dd, N, (const float*)gvec, sorted_n, gp, gps, scale_begin * NP,
-                            stb.per_scale);
+    if (gvec_bf16) hipLaunchKernelGGL((scatter_grouped_kernel<NP, __bf16>), L.grid, dim3(256), 0, st, L.dd, N, (const __bf16*)gvec, sorted_n, gp, L.gps, seg0,
+                                      L.st.per_scale);
+    else hipLaunchKernelGGL((scatter_grouped_kernel<NP, float>), L.grid, dim3(256), 0, st, L.dd, N, (const float*)gvec, sorted_n, gp, L.gps, seg0, L.st.per_scale);
     SNERF_LAUNCH_CHECK("kplanes_scatter_grouped");
     return 0;
   }
-  const int64_t threads = groups_per_seg * (scale_end - scale_begin) * NP * (2 * C);
-  if (gvec_bf16) hipLaunchKernelGGL((scatter_sorted_kernel<C, NP, __bf16>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, st, dd, N,
-                                    (const __bf16*)gvec, sorted_n, gp, run, groups_per_seg, scale_begin * NP, stb.per_scale);
-  else hipLaunchKernelGGL((scatter_sorted_kernel<C, NP, float>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, st, dd, N, (const float*)gvec,
-                          sorted_n, gp, run, groups_per_seg, scale_begin * NP, stb.per_scale);
+  constexpr int run = 256;  // entries per lane group, as the chunk kernels: L.gps groups per segment
+  const dim3 grid((unsigned)ceil_div(L.gps * (scale_end - scale_begin) * NP * (2 * C), 256));
+  if (gvec_bf16) hipLaunchKernelGGL((scatter_sorted_kernel<C, NP, __bf16>), grid, dim3(256), 0, st, L.dd, N, (const __bf16*)gvec, sorted_n, gp, run, L.gps, seg0,
+                                    L.st.per_scale);
+  else hipLaunchKernelGGL((scatter_sorted_kernel<C, NP, float>), grid, dim3(256), 0, st, L.dd, N, (const float*)gvec, sorted_n, gp, run, L.gps, seg0, L.st.per_scale);
   SNERF_LAUNCH_CHECK("kplanes_scatter_sorted");
   return 0;
 }
-
-#define DISPATCH2(FN, ...)                                                              \
-  do {                                                                                  \
-    if (desc->n_coords == 4) {                                                          \
-      if (desc->C == 32) return FN<32, 6>(__VA_ARGS__);                                 \
-      if (desc->C == 16) return FN<16, 6>(__VA_ARGS__);                                 \
-      return FN<8, 6>(__VA_ARGS__);                                                     \
-    } else {                                                                            \
-      if (desc->C == 32) return FN<32, 3>(__VA_ARGS__);                                 \
-      if (desc->C == 16) return FN<16, 3>(__VA_ARGS__);                                 \
-      return FN<8, 3>(__VA_ARGS__);                                                     \
-    }                                                                                   \
-  } while (0)
 
 extern "C" int snerf_kplanes_gradvec(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N, const float* grad_out,
                                      void* gvec, int32_t gvec_bf16, snerf_stream_t stream) {
@@ -996,7 +916,7 @@ extern "C" int snerf_kplanes_gradvec(const snerf_kplanes_desc* desc, const float
   if (rc) return rc;
   if (N == 0) return 0;
   SNERF_REQUIRE(planes && grad_out && gvec, "kplanes_gradvec: null buffer");
-  DISPATCH2(launch_gradvec, desc, planes, coords, N, grad_out, gvec, gvec_bf16, (hipStream_t)stream);
+  DISPATCH_C_NP(launch_gradvec, desc, planes, coords, N, grad_out, gvec, gvec_bf16, (hipStream_t)stream);
 }
 
 extern "C" int snerf_kplanes_scatter_sorted_scales(const snerf_kplanes_desc* desc, int64_t N, const void* gvec, int32_t gvec_bf16, const float* sorted_rec,
@@ -1008,7 +928,7 @@ extern "C" int snerf_kplanes_scatter_sorted_scales(const snerf_kplanes_desc* des
                 scale_begin, scale_end, desc->n_scales);
   if (N == 0 || scale_begin == scale_end) return 0;
   SNERF_REQUIRE(gvec && sorted_rec && grad_planes, "kplanes_scatter_sorted: null buffer");
-  DISPATCH2(launch_scatter_sorted, desc, N, gvec, gvec_bf16, reinterpret_cast<const float4*>(sorted_rec), grad_planes, scale_begin, scale_end,
+  DISPATCH_C_NP(launch_scatter_sorted, desc, N, gvec, gvec_bf16, reinterpret_cast<const float4*>(sorted_rec), grad_planes, scale_begin, scale_end,
             (hipStream_t)stream);
 }
 
@@ -1062,32 +982,23 @@ extern "C" int snerf_kplanes_scatter_quotient_scales(const snerf_kplanes_desc* d
                 scale_begin, scale_end, desc->n_scales);
   if (N == 0 || scale_begin == scale_end) return 0;
   SNERF_REQUIRE(planes && G && sorted_rec && grad_planes, "kplanes_scatter_quotient: null buffer");
-  snerf_kplanes_desc dd = *desc;
-  dd.n_scales = scale_end;
-  SegTable stb;
-  rc = build_segs(desc, stb);
-  if (rc) return rc;
-  const int NP = desc->n_coords == 4 ? 6 : 3;
-  for (int s = scale_begin; s < scale_end; ++s) {  // pass B addresses a plane's texels with 32-bit element offsets
-    int64_t mx = 1;
-    for (int k = 0; k < desc->n_coords; ++k) mx = mx > desc->res[s][k] ? mx : desc->res[s][k];
-    SNERF_REQUIRE(mx * mx * desc->C < (1LL << 31), "kplanes_scatter_quotient: plane of %lld^2 texels too large for 32-bit offsets", (long long)mx);
-  }
-  const int64_t gps = (N + 255) / 256;
-  const dim3 grid((unsigned)ceil_div(gps * (scale_end - scale_begin) * NP, 4));
-  const float4* rec = reinterpret_cast<const float4*>(sorted_rec);
   const int stride = desc->C * desc->n_scales;
+  PassBLaunch L;
+  rc = passb_launch_make(desc, N, scale_begin, scale_end, stride, L);
+  if (rc) return rc;
+  // scatter_grouped_kernel addresses a plane's texels with 32-bit element offsets
+  SNERF_REQUIRE(L.max_res * L.max_res * desc->C < (1LL << 31), "kplanes_scatter_quotient: plane of %lld^2 texels too large for 32-bit offsets",
+                (long long)L.max_res);
+  const int NP = L.st.n_planes, seg0 = scale_begin * NP;
+  const float4* rec = reinterpret_cast<const float4*>(sorted_rec);
   hipStream_t st = (hipStream_t)stream;
-  if ((int64_t)N * stride * 4 < (1LL << 32) && halfwave_ok(desc, scale_begin, scale_end)) {
-    if (NP == 6) hipLaunchKernelGGL((scatter_halfwave_kernel<6, true>), grid, dim3(256), 0, st, dd, N, G, rec, grad_planes, gps, scale_begin * NP, stb.per_scale, planes, stride);
-    else hipLaunchKernelGGL((scatter_halfwave_kernel<3, true>), grid, dim3(256), 0, st, dd, N, G, rec, grad_planes, gps, scale_begin * NP, stb.per_scale, planes, stride);
-    SNERF_LAUNCH_CHECK("kplanes_scatter_quotient");
-    return 0;
+  if (L.halfwave) {
+    if (NP == 6) hipLaunchKernelGGL((scatter_halfwave_kernel<6, true>), L.grid, dim3(256), 0, st, L.dd, N, G, rec, grad_planes, L.gps, seg0, L.st.per_scale, planes, stride);
+    else hipLaunchKernelGGL((scatter_halfwave_kernel<3, true>), L.grid, dim3(256), 0, st, L.dd, N, G, rec, grad_planes, L.gps, seg0, L.st.per_scale, planes, stride);
+  } else {
+    if (NP == 6) hipLaunchKernelGGL((scatter_grouped_kernel<6, float, true>), L.grid, dim3(256), 0, st, L.dd, N, G, rec, grad_planes, L.gps, seg0, L.st.per_scale, planes, stride);
+    else hipLaunchKernelGGL((scatter_grouped_kernel<3, float, true>), L.grid, dim3(256), 0, st, L.dd, N, G, rec, grad_planes, L.gps, seg0, L.st.per_scale, planes, stride);
   }
-  if (NP == 6) hipLaunchKernelGGL((scatter_grouped_kernel<6, float, true>), grid, dim3(256), 0, st, dd, N, G, rec, grad_planes, gps, scale_begin * NP, stb.per_scale,
-                                  planes, stride);
-  else hipLaunchKernelGGL((scatter_grouped_kernel<3, float, true>), grid, dim3(256), 0, st, dd, N, G, rec, grad_planes, gps, scale_begin * NP, stb.per_scale,
-                          planes, stride);
   SNERF_LAUNCH_CHECK("kplanes_scatter_quotient");
   return 0;
 }

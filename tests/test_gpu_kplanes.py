@@ -198,6 +198,20 @@ def test_quotient_scatter_equals_direct_scatter(ms, N, zeros):
     """Quotient form of the sorted scatter -- g_q = (gfeat .* feat) ./ v_q with v_q re-interpolated in pass B -- against the sample-major
     scatter and the product-form sorted scatter.  `zeros`: exact zeros planted in the planes, so that features vanish and the listed rows go
     through the exact fix-up (where the quotient alone would lose a plane's gradient)."""
+    _quotient_against_direct(ms, N, zeros, 4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ms,N,zeros,n_coords", [((1, 2), 1500, True, 4), ((1,), 257, True, 4), ((1,), 257, True, 3)])
+def test_quotient_fallback_kernel_equals_direct_scatter(ms, N, zeros, n_coords, monkeypatch):
+    """The same comparison, same bounds, with pass B forced onto scatter_grouped_kernel<NP, float, QUOT> -- the quotient form's kernel for
+    2^30 <= N * C * n_scales < 2^31, which no batch of a test's size reaches by itself.  The two smallest cases: a partial chunk (1500 = 5 * 256 +
+    220 entries per segment; 257 = one full chunk and a chunk of one entry and 255 null records) and zero texels; one of them on three planes."""
+    monkeypatch.setenv("SNERF_PASSB_GROUPED", "1")  # read by the library at every launch
+    _quotient_against_direct(ms, N, zeros, n_coords)
+
+
+def _quotient_against_direct(ms, N, zeros, n_coords):
     import ctypes as Ct
     from soccernerfs_amd import _lib, ops
     from soccernerfs_amd.plane_set import PlaneSet
@@ -205,7 +219,7 @@ def test_quotient_scatter_equals_direct_scatter(ms, N, zeros):
     dev = _dev()
     gen = torch.Generator().manual_seed(33)
     base = (11, 9, 7, 5) if N < 20000 else (64, 64, 64, 100)
-    ps = PlaneSet(32, [[r * m for r in base[:3]] + [base[3]] for m in ms], concat=True, generator=gen)
+    ps = PlaneSet(32, [[r * m for r in base[:3]] + [base[3]][: n_coords - 3] for m in ms], concat=True, generator=gen)
     with torch.no_grad():
         ps.planes.copy_(torch.rand(ps.numel, generator=gen) * 1.2 - 0.3)  # both signs, values near zero included
         if zeros:
@@ -218,6 +232,7 @@ def test_quotient_scatter_equals_direct_scatter(ms, N, zeros):
     pts = torch.rand(N, 4, generator=gen) * 2.2 - 1.1
     pts[: N // 3, 3] = 0.25
     pts[: N // 8] = pts[0]
+    pts = pts[:, :n_coords].contiguous()
     if zeros:
         pts[N // 2: N // 2 + 64] = -1.0  # the all-zero corner texel of plane 0 exactly (weights 1, 0, 0, 0)
         pts[N // 2 + 64: N // 2 + 96] = 1.0  # the subnormal last texel of plane 2 exactly
@@ -344,3 +359,122 @@ def test_quotient_scatter_with_one_subnormal_plane_value_beside_a_normal_feature
     assert float(b.abs().min()) > 1.0  # gfeat * (>= 32) summed over the cell's samples
     torch.testing.assert_close(a, b, rtol=2e-4, atol=0)
     torch.testing.assert_close(got, direct, rtol=1e-4, atol=2e-6 * float(direct.abs().max()))
+
+
+# ---- an exact lattice: every product and every sum is exact in fp32, so no route may differ from another in a single bit ----
+_LATTICE_RES = [[5, 5, 5, 3], [9, 9, 9, 3]]
+
+
+def _lattice_inputs(kind, C, concat, n_coords):
+    """kind "weights": planes all 1.0; coordinates from {-1.25, -1 + k/8 (k = 0..16), 1.25}, so every tap weight is a multiple of 1/8 (1/4 at
+    resolution 5, 1/2 at 9), every plane value is exactly 1 (and v_rcp_f32(1) = 1); N = 3001, |sum| <= 3001 * 8 units of 2^-9.
+    kind "values": coordinates on texel centres of both scales (space {-1, -0.5, 0, 0.5, 1}, time {-1, 0, 1}: weights 1 and 0), texels from
+    {0.5, 1, 2} with ~3 % exactly 0.0 (features vanish: the fix list and its one-zero / several-zeros branches run); N = 1500, a term is at most
+    8 * 2^5 in units of 2^-5: sums below 2^24 units.  grad_out: integers in [-8, 8]."""
+    from soccernerfs_amd.plane_set import PlaneSet
+
+    gen = torch.Generator().manual_seed(77 if kind == "weights" else 78)
+    ps = PlaneSet(C, [r[:n_coords] for r in _LATTICE_RES], concat=concat, generator=gen)
+    if kind == "weights":
+        N = 3001
+        choices = torch.tensor([-1.25] + [-1.0 + k / 8.0 for k in range(17)] + [1.25])
+        pts = choices[torch.randint(0, len(choices), (N, n_coords), generator=gen)]
+        with torch.no_grad():
+            ps.planes.fill_(1.0)
+    else:
+        N = 1500
+        pts = torch.tensor([-1.0, -0.5, 0.0, 0.5, 1.0])[torch.randint(0, 5, (N, n_coords), generator=gen)]
+        if n_coords == 4:
+            pts[:, 3] = torch.tensor([-1.0, 0.0, 1.0])[torch.randint(0, 3, (N,), generator=gen)]
+        with torch.no_grad():
+            ps.planes.copy_(torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (ps.numel,), generator=gen)])
+            ps.planes[torch.rand(ps.numel, generator=gen) < 0.03] = 0.0
+    gout = torch.randint(-8, 9, (N, ps.out_dim), generator=gen).to(torch.float32)
+    return ps, pts.contiguous(), gout
+
+
+def _lattice_oracle(ps, pts, gout):
+    """Plane gradients in float64 (autograd through the oracle's bilinear restatement, over this plane set's axis pairs), rounded to fp32."""
+    from oracle import kplanes_oracle as KO
+
+    grids = [[t.double().requires_grad_(True) for t in sc] for sc in ps.to_reference()]
+    p64 = pts.double()
+    outs = []
+    for sc in grids:
+        prod = 1.0
+        for plane, comb in zip(sc, ps.combs):
+            prod = prod * KO.bilinear_plane(plane, p64[:, list(comb)])
+        outs.append(prod)
+    feat = torch.cat(outs, dim=-1) if ps.concat else sum(outs)
+    feat.backward(gout.double())
+    flat = torch.zeros(ps.numel, dtype=torch.float64)
+    for s, sc in enumerate(grids):
+        for p, plane in enumerate(sc):
+            ps.plane_view(s, p, flat).copy_(plane.grad[0].permute(1, 2, 0))
+    return flat.to(torch.float32)
+
+
+def _lattice_routes(ps, pts, gout, monkeypatch):
+    """name -> plane gradients of every scatter route that supports the plane set, on the device."""
+    import ctypes as Ct
+    from soccernerfs_amd import _lib, ops
+
+    dev = _dev()
+    N = pts.shape[0]
+    ps = ps.to(dev)
+    ptsd, goutd = pts.to(dev), gout.to(dev)
+    co = ops.coords_from_points(ptsd)
+    desc = ps.desc()
+    L = _lib.lib()
+    out = {}
+    out["direct"] = torch.zeros_like(ps.planes)
+    _lib.check(L.snerf_kplanes_gather_bwd(Ct.byref(desc), ops._ptr(ps.planes), Ct.byref(co), Ct.c_int64(N), ops._ptr(goutd), ops._ptr(out["direct"]), ops._stream()))
+    fx = torch.zeros(ps.numel, dtype=torch.int64, device=dev)
+    _lib.check(L.snerf_kplanes_gather_bwd_fx(Ct.byref(desc), ops._ptr(ps.planes), Ct.byref(co), Ct.c_int64(N), ops._ptr(goutd), ops._ptr(fx), ops._stream()))
+    out["fixed_point"] = torch.zeros_like(ps.planes)
+    ops.fx_to_float(fx, out["fixed_point"])
+    quot = ps.C == 32 and ps.concat
+    feat = torch.empty(N, ps.out_dim, device=dev)
+    _lib.check(L.snerf_kplanes_gather_fwd(Ct.byref(desc), ops._ptr(ps.planes), Ct.byref(co), Ct.c_int64(N), ops._ptr(feat), ops._stream()))
+    n_fix = None
+    for grouped in (False, True):  # pass B: scatter_halfwave_kernel, then (C = 32) scatter_grouped_kernel through the library's switch
+        if grouped:
+            if ps.C != 32:
+                break
+            monkeypatch.setenv("SNERF_PASSB_GROUPED", "1")
+        tag = "_grouped" if grouped else ""
+        ss = ops.SortedScatter(ps, N, dev)
+        ss.sort(co)
+        out["sorted" + tag] = torch.zeros_like(ps.planes)
+        ss.scatter(ps.planes, co, goutd, out["sorted" + tag])
+        if quot:
+            sq = ops.SortedScatter(ps, N, dev, quotient=True)
+            sq.sort(co)
+            out["quotient" + tag] = torch.zeros_like(ps.planes)
+            sq.scatter_quotient(ps.planes, co, goutd, feat, out["quotient" + tag])
+            n_fix = int(sq.fix_count.item())
+    monkeypatch.delenv("SNERF_PASSB_GROUPED", raising=False)
+    return {k: v.detach().cpu() for k, v in out.items()}, n_fix
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["weights", "values"])
+@pytest.mark.parametrize("C,concat,n_coords", [(32, True, 4), (32, True, 3), (8, False, 4)])
+def test_every_scatter_route_is_exact_on_a_lattice(kind, C, concat, n_coords, monkeypatch):
+    """On these inputs every product and sum of the plane-gradient scatter is exact in fp32, so neither the order of the atomics nor the form
+    (product, quotient, fixed point) can change a bit: the direct scatter, its fixed-point form, the sorted product form (fp32 vectors) and, for
+    C = 32 with concatenated scales, the quotient form -- each sorted route through both pass-B kernels -- must all equal the float64 oracle
+    rounded to fp32."""
+    ps, pts, gout = _lattice_inputs(kind, C, concat, n_coords)
+    want = _lattice_oracle(ps, pts, gout)
+    assert float(want.abs().max()) > 0
+    got, n_fix = _lattice_routes(ps, pts, gout, monkeypatch)
+    expected = {"direct", "fixed_point", "sorted"} | ({"sorted_grouped"} if C == 32 else set()) | ({"quotient", "quotient_grouped"} if C == 32 and concat else set())
+    assert set(got) == expected
+    if C == 32 and concat:
+        assert (n_fix > 0) == (kind == "values")  # the planted zero texels reach the fix list
+    for name, g in got.items():
+        bad = int((g != want).sum())
+        print(f"{kind} C={C} n_coords={n_coords} {name}: {bad} of {g.numel()} cells differ from the oracle, max |diff| {float((g - want).abs().max()):.3g}")
+    for name, g in got.items():
+        assert torch.equal(g, want), name

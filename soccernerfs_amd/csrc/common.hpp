@@ -103,7 +103,7 @@ __device__ __forceinline__ void grad_add(float* g, long long* gfx, int64_t idx, 
 // rounding boundary (~1e-9 per element) -- indices stay bit-exact on every fixture and random test of the suite.
 //   in[0..n) (LDS) -> out[i] = (float) sum_{j <= i} in[j]   (EXCLUSIVE: sum_{j < i});  REVERSE: the same from the far end (suffix sums).
 // Returns the total in every lane.  in and out may alias (a lane reads and writes only its own block).
-constexpr int WSCAN_PER = 5;  // 64 * 5 = 320 = the per-ray kernels' MAX_S
+constexpr int WSCAN_PER = 5;  // elements per lane: MAX_S = 64 * WSCAN_PER = 320 samples per ray (per_ray_common.hpp)
 template <bool EXCLUSIVE, bool REVERSE>
 __device__ __forceinline__ double wave_scan_f64(const float* in, float* out, int n, int lane) {
   const int per = (n + 63) >> 6;

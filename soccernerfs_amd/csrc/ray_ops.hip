@@ -8,14 +8,11 @@
 //
 // Reference: NS/model_components/ray_samplers.py (SpacedSampler :79-126, PDFSampler :274-369,
 // ProposalNetworkSampler :584), NS/cameras/rays.py:127-149 (get_weights).
-#include "common.hpp"
+#include "per_ray_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace snerf {
-
-constexpr int RAYS_PER_BLOCK = 4;
-constexpr int MAX_S = 320;  // max samples per ray handled by the per-ray kernels
 
 __device__ __forceinline__ float spacing_fn(float x, int kind) {
   // kind 0: uniform (identity); kind 1: UniformLinDispPiecewise  x<1 ? x/2 : 1-1/(2x)  (ray_samplers.py:242)
@@ -98,21 +95,9 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
 
   // ---- stage 1: weights (or load them) ----
   if (a.density) {
-    for (int i = lane; i < Sp; i += 64) {
-      float e0 = a.ebins_prev[(int64_t)r * (Sp + 1) + i], e1 = a.ebins_prev[(int64_t)r * (Sp + 1) + i + 1];
-      w[i] = (e1 - e0) * a.density[(int64_t)r * Sp + i];  // delta * sigma
-    }
-    __syncthreads();
-    wave_scan_f64<true, false>(w, cdf, Sp, lane);  // exclusive cumsum of delta * sigma (rays.py:141-145), double accumulator as ATen's CPU cumsum
-    __syncthreads();
-    for (int i = lane; i < Sp; i += 64) {
-      float dd = w[i];
-      float alpha = 1.f - expf(-dd);
-      float T = expf(-cdf[i]);
-      float wt = nan_to_num(alpha * T);
-      w[i] = wt;
-      if (a.weights_out && live) a.weights_out[(int64_t)r * Sp + i] = wt;
-    }
+    // cdf holds the exclusive cumsum of delta * sigma on the way; the weights overwrite delta * sigma
+    ray_weights<BlockSync>(a.ebins_prev + (int64_t)r * (Sp + 1), a.density + (int64_t)r * Sp, Sp, w, cdf, w,
+                           a.weights_out ? a.weights_out + (int64_t)r * Sp : nullptr, live, Sp, lane);
   } else {
     for (int i = lane; i < Sp; i += 64) w[i] = a.weights_in[(int64_t)r * Sp + i];
   }
@@ -194,55 +179,9 @@ __global__ __launch_bounds__(256) void weights_bwd_kernel(const float* __restric
   const int r = live ? ray : R - 1;
   float* dd = s_a[wv];
   float* aux = s_b[wv];
-  for (int i = lane; i < S; i += 64) {
-    float e0 = ebins[(int64_t)r * (S + 1) + i], e1 = ebins[(int64_t)r * (S + 1) + i + 1];
-    dd[i] = (e1 - e0) * density[(int64_t)r * S + i];
-  }
-  __syncthreads();
-  wave_scan_f64<true, false>(dd, aux, S, lane);  // exclusive cumsum
-  __syncthreads();
-  // gw_i * w_i (0 where the forward weight was non-finite: nan_to_num passes no gradient there)
-  float gwterm[5], Tk[5], ek[5];
-  bool bad = false;  // a value that autograd would have turned into a non-finite gradient (the reference's GradScaler then skips the step)
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int i = lane + 64 * k;
-    gwterm[k] = 0.f; Tk[k] = 0.f; ek[k] = 0.f;
-    if (i < S) {
-      float T = expf(-aux[i]);
-      float e = expf(-dd[i]);
-      float wraw = (1.f - e) * T;
-      float g = gw[(int64_t)r * S + i];
-      bool fin = (wraw == wraw) && fabsf(wraw) != INFINITY;
-      Tk[k] = T; ek[k] = e;
-      gwterm[k] = fin ? g * wraw : 0.f;
-      // a non-finite weight (density = exp(x) overflowed to inf on a zero-width bin: 0 * inf) passes no gradient, as nan_to_num
-      // does -- and must not leave a NaN factor behind: 0 * NaN is NaN (seen once in ~20 k training steps: one NaN here reaches
-      // every parameter through the sigma net and the TV stencil within a few steps)
-      if (!fin) { Tk[k] = 0.f; ek[k] = 0.f; bad = bad || live; }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int i = lane + 64 * k;
-    if (i < S) aux[i] = gwterm[k];
-  }
-  __syncthreads();
-  wave_scan_f64<true, true>(aux, aux, S, lane);  // suffix sums: aux[i] = sum_{j > i}
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int i = lane + 64 * k;
-    if (i < S && live) {
-      float g = gw[(int64_t)r * S + i];
-      float e0 = ebins[(int64_t)r * (S + 1) + i], e1 = ebins[(int64_t)r * (S + 1) + i + 1];
-      float gdd = g * Tk[k] * ek[k] - aux[i];
-      float out = gdd * (e1 - e0);
-      if (!(fabsf(out) <= 3.402823466e+38f)) { out = 0.f; bad = true; }  // inf * 0 / NaN: no gradient (the reference's GradScaler skips such a step)
-      if (accumulate) gdens[(int64_t)r * S + i] += out; else gdens[(int64_t)r * S + i] = out;
-    }
-  }
+  const float* eb = ebins + (int64_t)r * (S + 1);
+  ray_optical_depth<BlockSync>(eb, density + (int64_t)r * S, S, dd, aux, S, lane);
+  const bool bad = ray_weights_bwd<BlockSync>(dd, aux, gw + (int64_t)r * S, eb, gdens + (int64_t)r * S, accumulate != 0, live, S, lane);
   if (bad && nonfinite_flag) *nonfinite_flag = 1;  // plain store of a constant: racing writers agree
 }
 

@@ -10,21 +10,21 @@
 // field_render_kernel: the tile of field_fused_common.hpp (the same code field_fwd_kernel runs, so the same density / colour bits) with another
 // work decomposition above it: a workgroup owns a WHOLE RAY and walks its 32-sample tiles front to back.  The ray's density [S], colour [S,3] and
 // bin edges [S+1] stay in LDS (7.7 KB at the limit S = 320, beside the ~43 KB of the tile: two workgroups per CU as before); per-sample density
-// and colour never reach HBM.  After the last tile wave 0 runs the per-ray arithmetic of resample_kernel stage 1 (snerf_weights_fwd) and
-// render_fwd_kernel (training = 0, bg_mode = 1) on the LDS-resident values in the same order (wave_scan_f64, the wave_sum reductions, products
-// rounded one by one), so the outputs equal the three-kernel chain bit for bit -- as ray_train_kernel restates the training step's five.
+// and colour never reach HBM.  After the last tile wave 0 runs the per-ray phases of resample_kernel stage 1 (snerf_weights_fwd) and
+// render_fwd_kernel (training = 0, bg_mode = 1) on the LDS-resident values -- the same functions of per_ray_common.hpp -- so the outputs equal
+// the three-kernel chain bit for bit, as ray_train_kernel's equal the training step's five.
 //
 // Early ray termination (transmittance_cutoff > 0): after a tile every wave forms the ray's remaining transmittance T = exp(-sum sigma delta) over
 // the samples evaluated so far (the same LDS values, the same arithmetic: the decision is workgroup-uniform without a broadcast).  If T < cutoff
 // the ray's remaining tiles are not gathered or decoded; their samples count as zero density, and the background is the last evaluated sample's
 // colour.  The weights that are dropped sum to less than T: |rgb error| <= cutoff per channel.  cutoff = 0 never terminates: the exact path.
 #include "field_fused_common.hpp"
+#include "per_ray_common.hpp"
 #include "raygen_common.hpp"
 
 namespace snerf {
 
-constexpr int RE_MAXS = 320;  // the per-ray kernels' limit (wave_scan_f64: 64 lanes x WSCAN_PER)
-constexpr size_t RAY_LDS_B = sizeof(float) * (RE_MAXS * 6 + 4);  // a ray's density / prefix sums / colour / bin edges behind the tile's LDS plan
+constexpr size_t RAY_LDS_B = sizeof(float) * (MAX_S * 6 + 4);  // a ray's density / prefix sums / colour / bin edges behind the tile's LDS plan
 
 struct FrameRaygenArgs {
   float fx, fy, cx, cy, c2w[12], time;
@@ -98,60 +98,24 @@ struct RayOut {
 };
 
 // One ray by ONE wavefront from LDS: dd holds the densities of the first `done` samples on entry (the rest count as zero), col the colours,
-// eb the S + 1 euclidean bin edges.  The statements and their order are those of resample_kernel stage 1 and render_fwd_kernel.
+// eb the S + 1 euclidean bin edges.  The phases of snerf_weights_fwd and of render_fwd_kernel in eval mode (per_ray_common.hpp), with the
+// wave's own barrier between them.
 __device__ __forceinline__ void composite_ray(float* dd, float* aux, const float* col, const float* eb, int S, int done, int64_t r, const RayOut& o,
                                               int lane) {
 #pragma clang fp contract(off)
-  // ---- get_weights (rays.py:127-149) ----
-  for (int i = lane; i < S; i += 64) {
-    const float e0 = eb[i], e1 = eb[i + 1];
-    dd[i] = (e1 - e0) * (i < done ? dd[i] : 0.f);  // delta * sigma
-  }
+  ray_weights<WaveSync>(eb, dd, done, dd, aux, dd, nullptr, false, S, lane);  // from here on dd holds the weights
   wave_lds_publish();
-  wave_scan_f64<true, false>(dd, aux, S, lane);
-  wave_lds_publish();
-  for (int i = lane; i < S; i += 64) {
-    const float d = dd[i];
-    const float alpha = 1.f - expf(-d);
-    const float T = expf(-aux[i]);
-    dd[i] = nan_to_num(alpha * T);  // from here on dd holds the weights
-  }
-  wave_lds_publish();
-  // ---- compositing, eval mode (renderers.py:113, :133-134, :214, :264-270) ----
-  const float* w = dd;
-  float cr = 0.f, cg = 0.f, cb = 0.f, acc = 0.f, dsum = 0.f;
-  for (int i = lane; i < S; i += 64) {
-    const float wi = w[i];
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (i < done) { x = nan_to_num(col[i * 3]); y = nan_to_num(col[i * 3 + 1]); z = nan_to_num(col[i * 3 + 2]); }
-    cr += wi * x; cg += wi * y; cb += wi * z;
-    acc += wi;
-    const float e0 = eb[i], e1 = eb[i + 1];
-    dsum += wi * ((e0 + e1) / 2.f);
-  }
-  cr = wave_sum(cr); cg = wave_sum(cg); cb = wave_sum(cb); acc = wave_sum(acc); dsum = wave_sum(dsum);
-  // median: first index with cumsum(w) >= 0.5 (searchsorted left), clamped; cumsum by wavefront scan in double
-  wave_scan_f64<false, false>(w, aux, S, lane);
-  wave_lds_publish();
-  int idx = S;
-  for (int i = lane; i < S; i += 64)
-    if (aux[i] >= 0.5f) { idx = i; break; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int t = __shfl_xor(idx, off, 64); idx = t < idx ? t : idx; }
-  if (idx > S - 1) idx = S - 1;
+  const RaySums s = ray_weighted_sums<true>(dd, nullptr, col, done, true, eb, S, lane);
+  const int idx = ray_median_index<WaveSync>(dd, aux, S, lane);
   if (lane == 0) {
-    const float* last = col + (done - 1) * 3;  // "last_sample" background: the last EVALUATED sample
-    const float b0 = nan_to_num(last[0]), b1 = nan_to_num(last[1]), b2 = nan_to_num(last[2]);
-    float o0 = cr + b0 * (1.f - acc), o1 = cg + b1 * (1.f - acc), o2 = cb + b2 * (1.f - acc);
-    o0 = fminf(fmaxf(o0, 0.f), 1.f); o1 = fminf(fmaxf(o1, 0.f), 1.f); o2 = fminf(fmaxf(o2, 0.f), 1.f);
-    o.rgb_out[r * 3] = o0; o.rgb_out[r * 3 + 1] = o1; o.rgb_out[r * 3 + 2] = o2;
-    o.acc_out[r] = acc;
+    float b[3], out[3];
+    ray_background(1, nullptr, r, col + (done - 1) * 3, true, b);  // "last_sample" background: the last EVALUATED sample
+    ray_blend(s, b, true, out);
+    o.rgb_out[r * 3] = out[0]; o.rgb_out[r * 3 + 1] = out[1]; o.rgb_out[r * 3 + 2] = out[2];
+    o.acc_out[r] = s.acc;
     if (o.median_index) o.median_index[r] = idx;
-    if (o.depth_median) {
-      const float e0 = eb[idx], e1 = eb[idx + 1];
-      o.depth_median[r] = (e0 + e1) / 2.f;
-    }
-    if (o.depth_expected) o.depth_expected[r] = dsum / (acc + 1e-10f);
+    if (o.depth_median) o.depth_median[r] = bin_midpoint(eb, idx);
+    if (o.depth_expected) o.depth_expected[r] = s.dsum / (s.acc + 1e-10f);
     if (o.samples_done) o.samples_done[r] = done;
   }
 }
@@ -168,10 +132,10 @@ template <typename T, int NS, bool VD>
 __global__ __launch_bounds__(FF_NW * 64, 4) void field_render_kernel(FieldArgs a, int R, RayOut o) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
-  float* s_dd = reinterpret_cast<float*>(smem_raw + PlanFF<NS>::BYTES);  // [RE_MAXS] density, then delta * sigma, then the weights
-  float* s_aux = s_dd + RE_MAXS;                                         // [RE_MAXS] the two prefix sums
-  float* s_col = s_aux + RE_MAXS;                                        // [RE_MAXS, 3]
-  float* s_eb = s_col + RE_MAXS * 3;                                     // [RE_MAXS + 1]
+  float* s_dd = reinterpret_cast<float*>(smem_raw + PlanFF<NS>::BYTES);  // [MAX_S] density, then delta * sigma, then the weights
+  float* s_aux = s_dd + MAX_S;                                           // [MAX_S] the two prefix sums
+  float* s_col = s_aux + MAX_S;                                          // [MAX_S, 3]
+  float* s_eb = s_col + MAX_S * 3;                                       // [MAX_S + 1]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int S = a.c.S, n_tiles = S / FF_TS;
   typename Ops<T>::v8 breg[NS];
@@ -218,7 +182,7 @@ static int launch_field_render(const FieldArgs& a, int R, const RayOut& o, hipSt
   return 0;
 }
 
-static bool render_shape_ok(int S) { return S >= FF_TS && S % FF_TS == 0 && S <= RE_MAXS; }
+static bool render_shape_ok(int S) { return S >= FF_TS && S % FF_TS == 0 && S <= MAX_S; }
 
 }  // namespace snerf
 
@@ -298,7 +262,7 @@ extern "C" int snerf_kplanes_field_render(const snerf_kplanes_desc* desc, const 
                                           int64_t* median_index, int32_t* samples_done, snerf_stream_t stream) {
   SNERF_REQUIRE(coords && R >= 0, "kplanes_field_render: null coords or R=%d", R);
   SNERF_REQUIRE(coords->mode == 1 && render_shape_ok(coords->S),
-                "kplanes_field_render: needs per-ray coordinates (coords.mode = 1) and S a multiple of %d, <= %d; got mode=%d S=%d", FF_TS, RE_MAXS,
+                "kplanes_field_render: needs per-ray coordinates (coords.mode = 1) and S a multiple of %d, <= %d; got mode=%d S=%d", FF_TS, MAX_S,
                 coords->mode, coords->S);
   int rc = validate_field(desc, coords, (int64_t)R * coords->S, sigma, color, 6);
   if (rc) return rc;

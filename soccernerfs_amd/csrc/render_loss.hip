@@ -5,14 +5,11 @@
 // :226-287, MedianRGBRenderer :290-362) and NS/model_components/losses.py (outer :46-75, lossfun_outer :78-95,
 // interlevel_loss :106-121, lossfun_distortion :125-136).  The reference's distortion loss materialises an
 // [R,S,S] tensor (67 MB at the preset); here the S x S interaction stays in LDS/registers.
-#include "common.hpp"
+#include "per_ray_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace snerf {
-
-constexpr int RPB = 4;
-constexpr int MAXS = 320;
 
 // ------------------------------------------------------------------------------------------------
 // render forward
@@ -32,66 +29,36 @@ struct RenderArgs {
 };
 
 __global__ __launch_bounds__(256) void render_fwd_kernel(RenderArgs a) {
-  __shared__ float s_w[RPB][MAXS];
-  __shared__ float s_cum[RPB][MAXS];
-  __shared__ int s_med[RPB];
+  __shared__ float s_w[RAYS_PER_BLOCK][MAX_S];
+  __shared__ float s_cum[RAYS_PER_BLOCK][MAX_S];
+  __shared__ int s_med[RAYS_PER_BLOCK];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   const bool live = ray < a.R;
   const int r = live ? ray : a.R - 1;
   const int S = a.S;
-  float cr = 0.f, cg = 0.f, cb = 0.f, acc = 0.f, dsum = 0.f;
-  for (int i = lane; i < S; i += 64) {
-    float w = a.weights[(int64_t)r * S + i];
-    s_w[wv][i] = w;
-    const float* c = a.rgb + ((int64_t)r * S + i) * 3;
-    float x = c[0], y = c[1], z = c[2];
-    if (!a.training) { x = nan_to_num(x); y = nan_to_num(y); z = nan_to_num(z); }  // renderers.py:133-134
-    cr += w * x; cg += w * y; cb += w * z;
-    acc += w;
-    float e0 = a.ebins[(int64_t)r * (S + 1) + i], e1 = a.ebins[(int64_t)r * (S + 1) + i + 1];
-    dsum += w * ((e0 + e1) / 2.f);
-  }
-  cr = wave_sum(cr); cg = wave_sum(cg); cb = wave_sum(cb); acc = wave_sum(acc); dsum = wave_sum(dsum);
+  const float* eb = a.ebins + (int64_t)r * (S + 1);
+  const float* rgb = a.rgb + (int64_t)r * S * 3;
+  const bool eval = !a.training;
+  const RaySums s = ray_weighted_sums<true>(a.weights + (int64_t)r * S, s_w[wv], rgb, S, eval, eb, S, lane);
   __syncthreads();
-  {
-    // median: first index with cumsum(w) >= 0.5 (searchsorted left), clamped (renderers.py:264-267); cumsum by wavefront scan in double
-    wave_scan_f64<false, false>(s_w[wv], s_cum[wv], S, lane);
-    __syncthreads();
-    int idx = S;
-    for (int i = lane; i < S; i += 64)
-      if (s_cum[wv][i] >= 0.5f) { idx = i; break; }  // the cumsum of non-negative weights is monotone: the lane's first hit is its smallest
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(idx, off, 64); idx = o < idx ? o : idx; }
-    if (idx > S - 1) idx = S - 1;
-    if (lane == 0) s_med[wv] = idx;
-  }
+  const int idx = ray_median_index<BlockSync>(s_w[wv], s_cum[wv], S, lane);
+  if (lane == 0) s_med[wv] = idx;
   __syncthreads();
   if (lane == 0 && live) {
-    const float* last = a.rgb + ((int64_t)r * S + (S - 1)) * 3;
-    float b0, b1, b2;
-    if (a.bg_mode == 0) { b0 = a.bg[(int64_t)r * 3]; b1 = a.bg[(int64_t)r * 3 + 1]; b2 = a.bg[(int64_t)r * 3 + 2]; }
-    else if (a.bg_mode == 1) {
-      b0 = last[0]; b1 = last[1]; b2 = last[2];
-      if (!a.training) { b0 = nan_to_num(b0); b1 = nan_to_num(b1); b2 = nan_to_num(b2); }
-    } else { b0 = a.bg[0]; b1 = a.bg[1]; b2 = a.bg[2]; }
-    float o0 = cr + b0 * (1.f - acc), o1 = cg + b1 * (1.f - acc), o2 = cb + b2 * (1.f - acc);  // renderers.py:113
-    if (!a.training) { o0 = fminf(fmaxf(o0, 0.f), 1.f); o1 = fminf(fmaxf(o1, 0.f), 1.f); o2 = fminf(fmaxf(o2, 0.f), 1.f); }
-    a.rgb_out[(int64_t)r * 3] = o0; a.rgb_out[(int64_t)r * 3 + 1] = o1; a.rgb_out[(int64_t)r * 3 + 2] = o2;
-    a.acc_out[r] = acc;
+    float b[3], o[3];
+    ray_background(a.bg_mode, a.bg, r, rgb + (S - 1) * 3, eval, b);
+    ray_blend(s, b, eval, o);
+    a.rgb_out[(int64_t)r * 3] = o[0]; a.rgb_out[(int64_t)r * 3 + 1] = o[1]; a.rgb_out[(int64_t)r * 3 + 2] = o[2];
+    a.acc_out[r] = s.acc;
     const int m = s_med[wv];
     if (a.median_index) a.median_index[r] = m;
-    if (a.depth_median) {
-      float e0 = a.ebins[(int64_t)r * (S + 1) + m], e1 = a.ebins[(int64_t)r * (S + 1) + m + 1];
-      a.depth_median[r] = (e0 + e1) / 2.f;
-    }
-    if (a.depth_expected) a.depth_expected[r] = dsum / (acc + 1e-10f);
+    if (a.depth_median) a.depth_median[r] = bin_midpoint(eb, m);
+    if (a.depth_expected) a.depth_expected[r] = s.dsum / (s.acc + 1e-10f);
     if (a.median_rgb) {
-      const float* c = a.rgb + ((int64_t)r * S + m) * 3;
+      const float* c = rgb + m * 3;
       float x = c[0], y = c[1], z = c[2];
-      if (!a.training) {
-        x = fminf(fmaxf(nan_to_num(x), 0.f), 1.f); y = fminf(fmaxf(nan_to_num(y), 0.f), 1.f); z = fminf(fmaxf(nan_to_num(z), 0.f), 1.f);
-      }
+      if (eval) { x = clamp01(nan_to_num(x)); y = clamp01(nan_to_num(y)); z = clamp01(nan_to_num(z)); }
       a.median_rgb[(int64_t)r * 3] = x; a.median_rgb[(int64_t)r * 3 + 1] = y; a.median_rgb[(int64_t)r * 3 + 2] = z;
     }
   }
@@ -104,16 +71,13 @@ __global__ void render_bwd_kernel(const float* __restrict__ weights, const float
   int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)R * S) return;
   int r = (int)(gid / S);
-  float go0 = g_rgb_out[(int64_t)r * 3], go1 = g_rgb_out[(int64_t)r * 3 + 1], go2 = g_rgb_out[(int64_t)r * 3 + 2];
-  float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-  if (bg_mode == 0) { b0 = bg[(int64_t)r * 3]; b1 = bg[(int64_t)r * 3 + 1]; b2 = bg[(int64_t)r * 3 + 2]; }
-  else if (bg_mode == 2) { b0 = bg[0]; b1 = bg[1]; b2 = bg[2]; }
-  const float* c = rgb + gid * 3;
-  float w = weights[gid];
-  float gw = go0 * (c[0] - b0) + go1 * (c[1] - b1) + go2 * (c[2] - b2);
+  const float go[3] = {g_rgb_out[(int64_t)r * 3], g_rgb_out[(int64_t)r * 3 + 1], g_rgb_out[(int64_t)r * 3 + 2]};
+  float b[3];
+  ray_background(bg_mode, bg, r, nullptr, false, b);
+  float gw = render_bwd_gw(go, rgb + gid * 3, b);
   if (g_acc) gw += g_acc[r];
   if (accumulate_w) g_weights[gid] += gw; else g_weights[gid] = gw;
-  if (g_rgb) { g_rgb[gid * 3] = go0 * w; g_rgb[gid * 3 + 1] = go1 * w; g_rgb[gid * 3 + 2] = go2 * w; }
+  if (g_rgb) render_bwd_grgb(go, weights[gid], g_rgb + gid * 3);
 }
 
 // render backward with the MSE image loss folded in: g_rgb_out = go_scale * (rgb_out - target) is formed per lane instead of by four
@@ -124,17 +88,12 @@ __global__ void render_mse_bwd_kernel(const float* __restrict__ weights, const f
   int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)R * S) return;
   int r = (int)(gid / S);
-  const float d0 = rgb_out[(int64_t)r * 3] - target[(int64_t)r * 3], d1 = rgb_out[(int64_t)r * 3 + 1] - target[(int64_t)r * 3 + 1],
-              d2 = rgb_out[(int64_t)r * 3 + 2] - target[(int64_t)r * 3 + 2];
-  if (sqerr_rays && gid == (int64_t)r * S) sqerr_rays[r] = (d0 * d0 + d1 * d1) + d2 * d2;
-  const float go0 = d0 * go_scale, go1 = d1 * go_scale, go2 = d2 * go_scale;
-  float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-  if (bg_mode == 0) { b0 = bg[(int64_t)r * 3]; b1 = bg[(int64_t)r * 3 + 1]; b2 = bg[(int64_t)r * 3 + 2]; }
-  else if (bg_mode == 2) { b0 = bg[0]; b1 = bg[1]; b2 = bg[2]; }
-  const float* c = rgb + gid * 3;
-  const float w = weights[gid];
-  g_weights[gid] = go0 * (c[0] - b0) + go1 * (c[1] - b1) + go2 * (c[2] - b2);
-  if (g_rgb) { g_rgb[gid * 3] = go0 * w; g_rgb[gid * 3 + 1] = go1 * w; g_rgb[gid * 3 + 2] = go2 * w; }
+  float go[3], b[3];
+  const float sqerr = mse_upstream(rgb_out + (int64_t)r * 3, target + (int64_t)r * 3, go_scale, go);
+  if (sqerr_rays && gid == (int64_t)r * S) sqerr_rays[r] = sqerr;
+  ray_background(bg_mode, bg, r, nullptr, false, b);
+  g_weights[gid] = render_bwd_gw(go, rgb + gid * 3, b);
+  if (g_rgb) render_bwd_grgb(go, weights[gid], g_rgb + gid * 3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -145,32 +104,15 @@ __global__ void render_mse_bwd_kernel(const float* __restrict__ weights, const f
 __global__ __launch_bounds__(256) void distortion_kernel(const float* __restrict__ weights, const float* __restrict__ sbins, int R, int S,
                                                         float grad_scale, float* __restrict__ loss_rays, float* __restrict__ g_weights,
                                                         int accumulate) {
-  __shared__ float s_w[RPB][MAXS];
-  __shared__ float s_m[RPB][MAXS];
+  __shared__ float s_w[RAYS_PER_BLOCK][MAX_S];
+  __shared__ float s_m[RAYS_PER_BLOCK][MAX_S];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   const bool live = ray < R;
   const int r = live ? ray : R - 1;
-  for (int i = lane; i < S; i += 64) {
-    float t0 = sbins[(int64_t)r * (S + 1) + i], t1 = sbins[(int64_t)r * (S + 1) + i + 1];
-    s_w[wv][i] = weights[(int64_t)r * S + i];
-    s_m[wv][i] = (t1 + t0) / 2.f;
-  }
-  __syncthreads();
-  float total = 0.f;
-  for (int i = lane; i < S; i += 64) {
-    const float wi = s_w[wv][i], mi = s_m[wv][i];
-    float inner = 0.f;
-    for (int j = 0; j < S; ++j) inner += s_w[wv][j] * fabsf(mi - s_m[wv][j]);
-    float t0 = sbins[(int64_t)r * (S + 1) + i], t1 = sbins[(int64_t)r * (S + 1) + i + 1];
-    float dt = t1 - t0;
-    total += wi * inner + wi * wi * dt / 3.f;
-    if (g_weights && live) {
-      float g = (2.f * inner + 2.f * wi * dt / 3.f) * grad_scale;
-      if (accumulate) g_weights[(int64_t)r * S + i] += g; else g_weights[(int64_t)r * S + i] = g;
-    }
-  }
-  total = wave_sum(total);
+  for (int i = lane; i < S; i += 64) s_w[wv][i] = weights[(int64_t)r * S + i];
+  const float total = ray_distortion<BlockSync>(s_w[wv], s_m[wv], sbins + (int64_t)r * (S + 1), grad_scale,
+                                                g_weights && live ? g_weights + (int64_t)r * S : nullptr, accumulate != 0, S, lane);
   if (lane == 0 && live && loss_rays) loss_rays[r] = total;
 }
 
@@ -184,13 +126,13 @@ __global__ __launch_bounds__(256) void distortion_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void interlevel_kernel(const float* __restrict__ c_bins, const float* __restrict__ w_nerf, int S,
                                                         const float* __restrict__ p_bins, const float* __restrict__ w_prop, int Sp, int R,
                                                         float grad_scale, float* __restrict__ loss_rays, float* __restrict__ g_wprop) {
-  __shared__ float s_tp[RPB][MAXS + 1];
-  __shared__ float s_cy[RPB][MAXS + 1];
-  __shared__ float s_g[RPB][MAXS];
-  __shared__ int s_lo[RPB][MAXS];
-  __shared__ int s_hi[RPB][MAXS];
+  __shared__ float s_tp[RAYS_PER_BLOCK][MAX_S + 1];
+  __shared__ float s_cy[RAYS_PER_BLOCK][MAX_S + 1];
+  __shared__ float s_g[RAYS_PER_BLOCK][MAX_S];
+  __shared__ int s_lo[RAYS_PER_BLOCK][MAX_S];
+  __shared__ int s_hi[RAYS_PER_BLOCK][MAX_S];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   const bool live = ray < R;
   const int r = live ? ray : R - 1;
   float* tp = s_tp[wv];
@@ -252,7 +194,7 @@ __global__ __launch_bounds__(256) void depth_loss_kernel(const float* __restrict
                                                         const float* __restrict__ dir_norm, float sigma, int R, int S, float grad_scale,
                                                         float* __restrict__ loss_rays, float* __restrict__ g_weights, int accumulate) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   if (ray >= R) return;
   float D = term[ray];
   if (dir_norm) D = D * dir_norm[ray];
@@ -286,7 +228,7 @@ __global__ __launch_bounds__(256) void urf_depth_loss_kernel(const float* __rest
                                                             float grad_scale, float* __restrict__ loss_rays, float* __restrict__ g_weights,
                                                             float* __restrict__ g_pred, int accumulate) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   if (ray >= R) return;
   float D = term[ray];
   if (dir_norm) D = D * dir_norm[ray];
@@ -324,9 +266,9 @@ __global__ __launch_bounds__(256) void urf_depth_loss_kernel(const float* __rest
 
 // ------------------------------------------------------------------------------------------------
 // One launch for the nerf level's per-ray work of a TRAINING step: get_weights -> RGB / accumulation / median depth -> MSE backward ->
-// distortion loss + gradient -> get_weights backward.  Same arithmetic, in the same order, as the five kernels it stands for
-// (resample_kernel stage 1, render_fwd_kernel, render_mse_bwd_kernel, distortion_kernel, weights_bwd_kernel: results are bit-identical,
-// tests/test_gpu_render_loss.py); on the step's critical path those five cost ~0.1 ms of launches and barriers for ~20 us of work.
+// distortion loss + gradient -> get_weights backward: the phases of per_ray_common.hpp that resample_kernel stage 1, render_fwd_kernel,
+// render_mse_bwd_kernel, distortion_kernel and weights_bwd_kernel run one by one (equal bits by construction; tests/test_gpu_render_loss.py
+// holds them to it).  On the step's critical path those five cost ~0.1 ms of launches and barriers for ~20 us of work.
 // ------------------------------------------------------------------------------------------------
 struct RayTrainArgs {
   const float* density; const float* ebins; const float* sbins; const float* rgb; const float* bg; const float* target;
@@ -337,146 +279,57 @@ struct RayTrainArgs {
 };
 
 __global__ __launch_bounds__(256) void ray_train_kernel(RayTrainArgs a) {
-  __shared__ float s_dd[RPB][MAXS + 1];   // delta * sigma
-  __shared__ float s_aux[RPB][MAXS + 1];  // exclusive cumsum of it; later the suffix sums of the backward
-  __shared__ float s_w[RPB][MAXS + 1];    // weights
-  __shared__ float s_m[RPB][MAXS + 1];    // cumsum of w (median), then the s-space bin midpoints
-  __shared__ float s_g[RPB][MAXS + 1];    // d loss / d weights
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ray = blockIdx.x * RPB + wv;
+  __shared__ float s_dd[RAYS_PER_BLOCK][MAX_S + 1];   // delta * sigma
+  __shared__ float s_aux[RAYS_PER_BLOCK][MAX_S + 1];  // exclusive cumsum of it; later the suffix sums of the backward
+  __shared__ float s_w[RAYS_PER_BLOCK][MAX_S + 1];    // weights
+  __shared__ float s_m[RAYS_PER_BLOCK][MAX_S + 1];    // cumsum of w (median), then the s-space bin midpoints
+  __shared__ float s_g[RAYS_PER_BLOCK][MAX_S + 1];    // d loss / d weights
+  // the wave index as a scalar: the ray's row pointers that the phases take then live in SGPRs, not in VGPR pairs beside the 15 floats the
+  // weights backward stages across its scan (80 VGPRs is the last count at which six waves per SIMD fit)
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int ray = blockIdx.x * RAYS_PER_BLOCK + wv;
   const bool live = ray < a.R;
   const int r = live ? ray : a.R - 1;
   const int S = a.S;
   float *dd = s_dd[wv], *aux = s_aux[wv], *w = s_w[wv], *mm = s_m[wv], *gw = s_g[wv];
   const float* eb = a.ebins + (int64_t)r * (S + 1);
 
-  // ---- get_weights (resample_kernel stage 1; rays.py:127-149) ----
-  for (int i = lane; i < S; i += 64) {
-    const float e0 = eb[i], e1 = eb[i + 1];
-    dd[i] = (e1 - e0) * a.density[(int64_t)r * S + i];
-  }
-  __syncthreads();
-  wave_scan_f64<true, false>(dd, aux, S, lane);
-  __syncthreads();
-  for (int i = lane; i < S; i += 64) {
-    const float alpha = 1.f - expf(-dd[i]);
-    const float T = expf(-aux[i]);
-    const float wt = nan_to_num(alpha * T);
-    w[i] = wt;
-    if (live) a.weights[(int64_t)r * S + i] = wt;
-  }
+  // ---- get_weights; dd and aux stay for the backward ----
+  ray_weights<BlockSync>(eb, a.density + (int64_t)r * S, S, dd, aux, w, a.weights + (int64_t)r * S, live, S, lane);
   __syncthreads();
 
-  // ---- render forward, training mode (render_fwd_kernel) ----
-  float cr = 0.f, cg = 0.f, cb = 0.f, acc = 0.f;
-  for (int i = lane; i < S; i += 64) {
-    const float wi = w[i];
-    const float* c = a.rgb + ((int64_t)r * S + i) * 3;
-    const float x = c[0], y = c[1], z = c[2];
-    cr += wi * x; cg += wi * y; cb += wi * z;
-    acc += wi;
-  }
-  cr = wave_sum(cr); cg = wave_sum(cg); cb = wave_sum(cb); acc = wave_sum(acc);
+  // ---- render forward, training mode ----
+  const float* rgb = a.rgb + (int64_t)r * S * 3;
+  const RaySums s = ray_weighted_sums<false>(w, nullptr, rgb, S, false, nullptr, S, lane);
   if (a.depth_median) {
-    wave_scan_f64<false, false>(w, mm, S, lane);
-    __syncthreads();
-    int idx = S;
-    for (int i = lane; i < S; i += 64)
-      if (mm[i] >= 0.5f) { idx = i; break; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(idx, off, 64); idx = o < idx ? o : idx; }
-    if (idx > S - 1) idx = S - 1;
-    if (lane == 0 && live) {
-      const float e0 = eb[idx], e1 = eb[idx + 1];
-      a.depth_median[r] = (e0 + e1) / 2.f;
-    }
+    const int idx = ray_median_index<BlockSync>(w, mm, S, lane);
+    if (lane == 0 && live) a.depth_median[r] = bin_midpoint(eb, idx);
     __syncthreads();
   }
-  float b0, b1, b2;
-  if (a.bg_mode == 0) { b0 = a.bg[(int64_t)r * 3]; b1 = a.bg[(int64_t)r * 3 + 1]; b2 = a.bg[(int64_t)r * 3 + 2]; }
-  else { b0 = a.bg[0]; b1 = a.bg[1]; b2 = a.bg[2]; }
-  const float o0 = cr + b0 * (1.f - acc), o1 = cg + b1 * (1.f - acc), o2 = cb + b2 * (1.f - acc);
+  float b[3], o[3], go[3];
+  ray_background(a.bg_mode, a.bg, r, nullptr, false, b);
+  ray_blend(s, b, false, o);
   if (lane == 0 && live) {
-    a.rgb_out[(int64_t)r * 3] = o0; a.rgb_out[(int64_t)r * 3 + 1] = o1; a.rgb_out[(int64_t)r * 3 + 2] = o2;
-    a.acc_out[r] = acc;
+    a.rgb_out[(int64_t)r * 3] = o[0]; a.rgb_out[(int64_t)r * 3 + 1] = o[1]; a.rgb_out[(int64_t)r * 3 + 2] = o[2];
+    a.acc_out[r] = s.acc;
   }
 
-  // ---- MSE folded into the render backward (render_mse_bwd_kernel) ----
-  const float d0 = o0 - a.target[(int64_t)r * 3], d1 = o1 - a.target[(int64_t)r * 3 + 1], d2 = o2 - a.target[(int64_t)r * 3 + 2];
-  if (lane == 0 && live && a.sqerr_rays) a.sqerr_rays[r] = (d0 * d0 + d1 * d1) + d2 * d2;
-  const float go0 = d0 * a.go_scale, go1 = d1 * a.go_scale, go2 = d2 * a.go_scale;
+  // ---- MSE folded into the render backward ----
+  const float sqerr = mse_upstream(o, a.target + (int64_t)r * 3, a.go_scale, go);
+  if (lane == 0 && live && a.sqerr_rays) a.sqerr_rays[r] = sqerr;
   for (int i = lane; i < S; i += 64) {
-    const float* c = a.rgb + ((int64_t)r * S + i) * 3;
-    gw[i] = go0 * (c[0] - b0) + go1 * (c[1] - b1) + go2 * (c[2] - b2);
-    if (live) {
-      float* g = a.g_rgb + ((int64_t)r * S + i) * 3;
-      const float wi = w[i];
-      g[0] = go0 * wi; g[1] = go1 * wi; g[2] = go2 * wi;
-    }
+    gw[i] = render_bwd_gw(go, rgb + i * 3, b);
+    if (live) render_bwd_grgb(go, w[i], a.g_rgb + ((int64_t)r * S + i) * 3);
   }
 
-  // ---- distortion loss and its gradient, added to gw (distortion_kernel with accumulate = 1) ----
-  const float* sb = a.sbins + (int64_t)r * (S + 1);
-  for (int i = lane; i < S; i += 64) {
-    const float t0 = sb[i], t1 = sb[i + 1];
-    mm[i] = (t1 + t0) / 2.f;
-  }
-  __syncthreads();
-  float total = 0.f;
-  for (int i = lane; i < S; i += 64) {
-    const float wi = w[i], mi = mm[i];
-    float inner = 0.f;
-    for (int j = 0; j < S; ++j) inner += w[j] * fabsf(mi - mm[j]);
-    const float t0 = sb[i], t1 = sb[i + 1];
-    const float dt = t1 - t0;
-    total += wi * inner + wi * wi * dt / 3.f;
-    const float g = (2.f * inner + 2.f * wi * dt / 3.f) * a.dist_scale;
-    gw[i] += g;
-  }
-  total = wave_sum(total);
+  // ---- distortion loss and its gradient, added to gw ----
+  const float total = ray_distortion<BlockSync>(w, mm, a.sbins + (int64_t)r * (S + 1), a.dist_scale, gw, true, S, lane);
   if (lane == 0 && live && a.dist_rays) a.dist_rays[r] = total;
   if (a.g_weights && live)
     for (int i = lane; i < S; i += 64) a.g_weights[(int64_t)r * S + i] = gw[i];
 
-  // ---- get_weights backward (weights_bwd_kernel) ----
-  float gwterm[5], Tk[5], ek[5];
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const int i = lane + 64 * k;
-    gwterm[k] = 0.f; Tk[k] = 0.f; ek[k] = 0.f;
-    if (i < S) {
-      const float T = expf(-aux[i]);
-      const float e = expf(-dd[i]);
-      const float wraw = (1.f - e) * T;
-      const float g = gw[i];
-      const bool fin = (wraw == wraw) && fabsf(wraw) != INFINITY;
-      Tk[k] = T; ek[k] = e;
-      gwterm[k] = fin ? g * wraw : 0.f;
-      if (!fin) { Tk[k] = 0.f; ek[k] = 0.f; bad = bad || live; }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const int i = lane + 64 * k;
-    if (i < S) aux[i] = gwterm[k];
-  }
-  __syncthreads();
-  wave_scan_f64<true, true>(aux, aux, S, lane);  // suffix sums: aux[i] = sum_{j > i}
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const int i = lane + 64 * k;
-    if (i < S && live) {
-      const float g = gw[i];
-      const float e0 = eb[i], e1 = eb[i + 1];
-      const float gdd = g * Tk[k] * ek[k] - aux[i];
-      float out = gdd * (e1 - e0);
-      if (!(fabsf(out) <= 3.402823466e+38f)) { out = 0.f; bad = true; }
-      a.g_density[(int64_t)r * S + i] = out;
-    }
-  }
+  // ---- get_weights backward ----
+  const bool bad = ray_weights_bwd<BlockSync>(dd, aux, gw, eb, a.g_density + (int64_t)r * S, false, live, S, lane);
   if (bad && a.nonfinite_flag) *a.nonfinite_flag = 1;
 }
 
@@ -486,10 +339,10 @@ using namespace snerf;
 
 extern "C" int snerf_depth_loss(const float* weights, const float* ebins, const float* termination_depth, const float* directions_norm, float sigma,
                                 int32_t R, int32_t S, float grad_scale, float* loss_rays, float* g_weights, int32_t accumulate, snerf_stream_t stream) {
-  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAXS && sigma > 0.f, "depth_loss: R=%d S=%d sigma=%g", R, S, (double)sigma);
+  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAX_S && sigma > 0.f, "depth_loss: R=%d S=%d sigma=%g", R, S, (double)sigma);
   if (R == 0) return 0;
   SNERF_REQUIRE(weights && ebins && termination_depth, "depth_loss: null buffer");
-  hipLaunchKernelGGL(depth_loss_kernel, dim3(ceil_div(R, RPB)), dim3(256), 0, (hipStream_t)stream, weights, ebins, termination_depth, directions_norm, sigma,
+  hipLaunchKernelGGL(depth_loss_kernel, dim3(ceil_div(R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, weights, ebins, termination_depth, directions_norm, sigma,
                      R, S, grad_scale, loss_rays, g_weights, accumulate);
   SNERF_LAUNCH_CHECK("depth_loss");
   return 0;
@@ -498,10 +351,10 @@ extern "C" int snerf_depth_loss(const float* weights, const float* ebins, const 
 extern "C" int snerf_urf_depth_loss(const float* weights, const float* ebins, const float* termination_depth, const float* directions_norm,
                                     const float* predicted_depth, float sigma, int32_t R, int32_t S, float grad_scale, float* loss_rays, float* g_weights,
                                     float* g_predicted_depth, int32_t accumulate, snerf_stream_t stream) {
-  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAXS && sigma > 0.f, "urf_depth_loss: R=%d S=%d sigma=%g", R, S, (double)sigma);
+  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAX_S && sigma > 0.f, "urf_depth_loss: R=%d S=%d sigma=%g", R, S, (double)sigma);
   if (R == 0) return 0;
   SNERF_REQUIRE(weights && ebins && termination_depth && predicted_depth, "urf_depth_loss: null buffer");
-  hipLaunchKernelGGL(urf_depth_loss_kernel, dim3(ceil_div(R, RPB)), dim3(256), 0, (hipStream_t)stream, weights, ebins, termination_depth, directions_norm,
+  hipLaunchKernelGGL(urf_depth_loss_kernel, dim3(ceil_div(R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, weights, ebins, termination_depth, directions_norm,
                      predicted_depth, sigma, R, S, grad_scale, loss_rays, g_weights, g_predicted_depth, accumulate);
   SNERF_LAUNCH_CHECK("urf_depth_loss");
   return 0;
@@ -509,7 +362,7 @@ extern "C" int snerf_urf_depth_loss(const float* weights, const float* ebins, co
 
 extern "C" int snerf_render_fwd(const snerf_render_args* p, snerf_stream_t stream) {
   SNERF_REQUIRE(p, "render_fwd: null args");
-  SNERF_REQUIRE(p->R >= 0 && p->S >= 1 && p->S <= MAXS, "render_fwd: R=%d S=%d (S <= %d)", p->R, p->S, MAXS);
+  SNERF_REQUIRE(p->R >= 0 && p->S >= 1 && p->S <= MAX_S, "render_fwd: R=%d S=%d (S <= %d)", p->R, p->S, MAX_S);
   SNERF_REQUIRE(p->bg_mode >= 0 && p->bg_mode <= 2, "render_fwd: bg_mode=%d", p->bg_mode);
   if (p->R == 0) return 0;
   SNERF_REQUIRE(p->weights && p->rgb && p->ebins && p->rgb_out && p->acc_out, "render_fwd: null buffer");
@@ -518,7 +371,7 @@ extern "C" int snerf_render_fwd(const snerf_render_args* p, snerf_stream_t strea
   a.weights = p->weights; a.rgb = p->rgb; a.ebins = p->ebins; a.bg = p->bg; a.R = p->R; a.S = p->S; a.bg_mode = p->bg_mode;
   a.training = p->training; a.rgb_out = p->rgb_out; a.acc_out = p->acc_out; a.depth_median = p->depth_median;
   a.depth_expected = p->depth_expected; a.median_rgb = p->median_rgb; a.median_index = p->median_index;
-  hipLaunchKernelGGL(render_fwd_kernel, dim3(ceil_div(p->R, RPB)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(render_fwd_kernel, dim3(ceil_div(p->R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, a);
   SNERF_LAUNCH_CHECK("render_fwd");
   return 0;
 }
@@ -551,10 +404,10 @@ extern "C" int snerf_render_mse_bwd(const float* weights, const float* rgb, cons
 
 extern "C" int snerf_distortion(const float* weights, const float* sbins, int32_t R, int32_t S, float grad_scale, float* loss_rays,
                                 float* g_weights, int32_t accumulate, snerf_stream_t stream) {
-  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAXS, "distortion: R=%d S=%d (S <= %d)", R, S, MAXS);
+  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAX_S, "distortion: R=%d S=%d (S <= %d)", R, S, MAX_S);
   if (R == 0) return 0;
   SNERF_REQUIRE(weights && sbins, "distortion: null buffer");
-  hipLaunchKernelGGL(distortion_kernel, dim3(ceil_div(R, RPB)), dim3(256), 0, (hipStream_t)stream, weights, sbins, R, S, grad_scale, loss_rays,
+  hipLaunchKernelGGL(distortion_kernel, dim3(ceil_div(R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, weights, sbins, R, S, grad_scale, loss_rays,
                      g_weights, accumulate);
   SNERF_LAUNCH_CHECK("distortion");
   return 0;
@@ -562,10 +415,10 @@ extern "C" int snerf_distortion(const float* weights, const float* sbins, int32_
 
 extern "C" int snerf_interlevel(const float* c_bins, const float* w_nerf, int32_t S, const float* p_bins, const float* w_prop, int32_t Sp,
                                 int32_t R, float grad_scale, float* loss_rays, float* g_wprop, snerf_stream_t stream) {
-  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAXS && Sp >= 1 && Sp <= MAXS, "interlevel: R=%d S=%d Sp=%d", R, S, Sp);
+  SNERF_REQUIRE(R >= 0 && S >= 1 && S <= MAX_S && Sp >= 1 && Sp <= MAX_S, "interlevel: R=%d S=%d Sp=%d", R, S, Sp);
   if (R == 0) return 0;
   SNERF_REQUIRE(c_bins && w_nerf && p_bins && w_prop, "interlevel: null buffer");
-  hipLaunchKernelGGL(interlevel_kernel, dim3(ceil_div(R, RPB)), dim3(256), 0, (hipStream_t)stream, c_bins, w_nerf, S, p_bins, w_prop, Sp, R,
+  hipLaunchKernelGGL(interlevel_kernel, dim3(ceil_div(R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, c_bins, w_nerf, S, p_bins, w_prop, Sp, R,
                      grad_scale, loss_rays, g_wprop);
   SNERF_LAUNCH_CHECK("interlevel");
   return 0;
@@ -573,7 +426,7 @@ extern "C" int snerf_interlevel(const float* c_bins, const float* w_nerf, int32_
 
 extern "C" int snerf_ray_train_fwd_bwd(const snerf_ray_train_args* p, snerf_stream_t stream) {
   SNERF_REQUIRE(p, "ray_train_fwd_bwd: null args");
-  SNERF_REQUIRE(p->R >= 0 && p->S >= 1 && p->S <= MAXS, "ray_train_fwd_bwd: R=%d S=%d (S <= %d)", p->R, p->S, MAXS);
+  SNERF_REQUIRE(p->R >= 0 && p->S >= 1 && p->S <= MAX_S, "ray_train_fwd_bwd: R=%d S=%d (S <= %d)", p->R, p->S, MAX_S);
   SNERF_REQUIRE(p->bg_mode == 0 || p->bg_mode == 2, "ray_train_fwd_bwd: bg_mode %d has no training backward", p->bg_mode);
   if (p->R == 0) return 0;
   SNERF_REQUIRE(p->density && p->ebins && p->sbins && p->rgb && p->bg && p->target && p->weights && p->rgb_out && p->acc_out && p->g_rgb && p->g_density,
@@ -583,7 +436,7 @@ extern "C" int snerf_ray_train_fwd_bwd(const snerf_ray_train_args* p, snerf_stre
   a.R = p->R; a.S = p->S; a.bg_mode = p->bg_mode; a.go_scale = p->go_scale; a.dist_scale = p->dist_scale;
   a.weights = p->weights; a.rgb_out = p->rgb_out; a.acc_out = p->acc_out; a.depth_median = p->depth_median; a.sqerr_rays = p->sqerr_rays;
   a.dist_rays = p->dist_rays; a.g_rgb = p->g_rgb; a.g_density = p->g_density; a.g_weights = p->g_weights; a.nonfinite_flag = p->nonfinite_flag;
-  hipLaunchKernelGGL(ray_train_kernel, dim3(ceil_div(p->R, RPB)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(ray_train_kernel, dim3(ceil_div(p->R, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, a);
   SNERF_LAUNCH_CHECK("ray_train_fwd_bwd");
   return 0;
 }

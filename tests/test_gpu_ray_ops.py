@@ -252,6 +252,35 @@ def test_weights_bwd_with_overflowed_density_stays_finite():
     torch.testing.assert_close(out[3:].cpu(), dr.grad, rtol=1e-4, atol=1e-6)
 
 
+@pytest.mark.parametrize("S,R", [(65, 3), (320, 5)])
+def test_weights_bwd_accumulate_adds_onto_the_prefill(S, R):
+    """accumulate = 1 onto a prefilled buffer is the prefill plus the accumulate = 0 result, bit for bit: one fp32 add per element.  Rows
+    behind R hold a sentinel and must stay untouched in both calls (R is no multiple of the four rays of a workgroup: a dead wave runs)."""
+    from soccernerfs_amd import _lib, ops
+    from tests import per_ray_reference as PR
+
+    GUARD, DEAD = 4, -7777.0
+    case = PR.pipeline_case(R, S, S, "a")
+    d, e = case["density"].to(DEV), case["ebins"].to(DEV)
+    g = (torch.rand(R, S, generator=torch.Generator().manual_seed(S + R)) - 0.5).to(DEV)
+    prefill = PR.prefill_like(torch.ones(R, S), "weights_bwd", S, R).to(DEV)
+    lib = _lib.lib()
+
+    def call(accumulate):
+        buf = torch.full((R + GUARD, S), DEAD, device=DEV)
+        buf[:R] = prefill
+        flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+        _lib.check(lib.snerf_weights_bwd(ops._ptr(d), ops._ptr(e), ops._ptr(g), R, S, ops._ptr(buf), accumulate, ops._ptr(flag), ops._stream()))
+        torch.cuda.synchronize()
+        assert bool((buf[R:] == DEAD).all()), f"accumulate = {accumulate}: rows behind R were written"
+        assert int(flag) == 0  # finite inputs
+        return buf[:R].clone()
+
+    plain, added = call(0), call(1)
+    assert bool((plain != prefill).any()) and bool(torch.isfinite(plain).all())
+    assert torch.equal(added, prefill + plain)
+
+
 def test_adam_drops_non_finite_gradient_elements():
     from soccernerfs_amd import ops
 

@@ -38,7 +38,8 @@ typedef void* snerf_stream_t; /* hipStream_t */
  * cameras), added WITHOUT counting a revision: callers and tests pin revision 2.  The binding lists them among the symbols it requires, so a
  * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call.
  * The same holds for snerf_mask_pack and snerf_sample_pixels_masked (pixel draws inside image masks), and for snerf_kplanes_gather_bwd_coords,
- * snerf_pose_apply and snerf_raygen_pose_bwd (the camera optimiser: coordinate gradients of the plane gather down to SO3xR3 pose deltas). */
+ * snerf_pose_apply and snerf_raygen_pose_bwd (the camera optimiser: coordinate gradients of the plane gather down to SO3xR3 pose deltas), and for
+ * snerf_ray_time_order and snerf_kplanes_field_fwd_ordered (the fused field forward's tiles walked in order of frame time). */
 #define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
@@ -286,6 +287,19 @@ int snerf_kplanes_field_fwd_supported(const snerf_kplanes_desc* desc, const sner
 int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
                             const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
                             float* density, float* rgb, void* feat16, float* h, float* feat32, snerf_stream_t stream);
+/* ABI 16 revision 2 (added to its surface, see SNERF_ABI_REVISION): the same kernel with its 32-sample tiles walked in the order of a ray
+ * permutation, ray_order int32 [R] (R = N / S; what snerf_ray_time_order writes).  All samples of a ray share t, so with the rays in order of
+ * frame time the workgroups resident at one moment read the same few texel rows of the XT / YT / ZT planes, which then stay in L2.  Only the
+ * walk changes: every sample's outputs land in that sample's own rows, so all outputs equal snerf_kplanes_field_fwd's bit for bit, and every
+ * other kernel of the step keeps seeing the batch in the order it was drawn.
+ *   ray_order == NULL: snerf_kplanes_field_fwd exactly.
+ *   ray_order != NULL: needs coords.mode == 1 and S % 32 == 0 (a tile is then 32 samples of one ray); anything else is an argument error.
+ * DEVICE DATA: the kernel does not validate the order's contents; it must be a permutation of 0..R-1 (an entry outside that range makes the
+ * kernel read and write out of bounds).  The trainer passes what snerf_ray_time_order wrote. */
+int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
+                                    const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
+                                    float* density, float* rgb, void* feat16, float* h, float* feat32, const int32_t* ray_order,
+                                    snerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ABI 16 revision 1: the render tail of the K-Planes model in eval mode as ONE kernel, for whole frames (ns-render / ns-eval: scripts/render.py:60-131,
@@ -795,6 +809,12 @@ int snerf_sample_pixels_masked(const float* u, int32_t R, int32_t M, int32_t H, 
  * R <= 16384 (one workgroup sorts in LDS). */
 int snerf_sort_rays_by_key(const int64_t* indices_in, const int32_t* image_key, int32_t n_keys, int32_t R, const float* aux_in, int32_t aux_cols,
                            int64_t* indices_out, float* aux_out, snerf_stream_t stream);
+
+/* ABI 16 revision 2 (added to its surface): order_out int32 [R] = the permutation of 0..R-1 that sorts times [R] ascending, ties by ray index, so
+ * a pure function of the batch.  The batch itself stays as drawn; the order is for snerf_kplanes_field_fwd_ordered.  Times are non-negative
+ * ([0,1]), so their bit patterns are compared as unsigned integers; nothing about them is checked on the device (any bits give a permutation).
+ * One 256-thread workgroup sorts in LDS: R <= 16384, more is an argument error. */
+int snerf_ray_time_order(const float* times, int32_t R, int32_t* order_out, snerf_stream_t stream);
 
 /* AABBBoxCollider alone: aabb6 = HOST pointer to {min x,y,z, max x,y,z}. */
 int snerf_aabb_collide(const float* origins, const float* dirs, int32_t R, const float* aabb6, float near_plane, int32_t training,

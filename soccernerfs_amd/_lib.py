@@ -169,7 +169,8 @@ def lib():
     l = C.CDLL(LIB_PATH)
     # entries added to revision 2's surface without a new revision number: a library from before them must fail here, not at the first call
     missing = [s for s in ("snerf_raygen_cam", "snerf_raygen_frame_cam", "snerf_sample_pixels_sphere", "snerf_mask_pack", "snerf_sample_pixels_masked",
-                                "snerf_kplanes_gather_bwd_coords", "snerf_pose_apply", "snerf_raygen_pose_bwd")
+                                "snerf_kplanes_gather_bwd_coords", "snerf_pose_apply", "snerf_raygen_pose_bwd", "snerf_ray_time_order",
+                                "snerf_kplanes_field_fwd_ordered")
                if not hasattr(l, s)]
     if missing:
         raise RuntimeError(f"libsnerf at {LIB_PATH} lacks {', '.join(missing)} (ABI {ABI_VERSION} revision {ABI_REVISION}): rebuild the library")
@@ -230,6 +231,8 @@ def lib():
     l.snerf_kplanes_gather_bwd_coords.argtypes = [P, P, P, L, P, P, P, P, P]
     l.snerf_pose_apply.argtypes = [P, P, P, I, I, P, P]
     l.snerf_raygen_pose_bwd.argtypes = [P, P]
+    l.snerf_ray_time_order.argtypes = [P, I, P, P]
+    l.snerf_kplanes_field_fwd_ordered.argtypes = [P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]
     if l.snerf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
     revision = l.snerf_abi_revision() if hasattr(l, "snerf_abi_revision") else 0  # a library from before revisions were counted
@@ -291,6 +294,7 @@ EXPORTS = [
     "snerf_mask_pack",
     "snerf_sample_pixels_masked",
     "snerf_sort_rays_by_key",
+    "snerf_ray_time_order",
     "snerf_kplanes_scatter_sorted_scales",
     "snerf_raygen",
     "snerf_raygen_frame",
@@ -339,6 +343,7 @@ EXPORTS = [
     "snerf_urf_depth_loss",
     "snerf_kplanes_field_fwd",
     "snerf_kplanes_field_fwd_supported",
+    "snerf_kplanes_field_fwd_ordered",
     "snerf_kplanes_field_render",
     "snerf_kplanes_field_render_supported",
     "snerf_kplanes_color_input_fwd",

@@ -32,6 +32,39 @@ __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, i
         [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
 }
 
+// The same tiles walked in the order of a ray permutation (snerf_kplanes_field_fwd_ordered: coords.mode = 1 and S % 32 == 0, so a tile is 32 samples
+// of ONE ray): with tpr = S / 32, tile k of the walk is sub-tile k % tpr of ray ray_order[k / tpr].  All samples of a ray share t, so with the rays in
+// order of frame time the tiles resident at one moment read the same two texel rows of every XT / YT / ZT plane.  Every sample's outputs go to that
+// sample's own rows, whatever the walk: the results are those of field_fwd_kernel bit for bit.  A kernel of its own, so that field_fwd_kernel keeps
+// its arguments and its registers.
+template <typename T, int NS, int KEEP = 0, bool VD = false>
+__global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_ordered_kernel(FieldArgs a, uint32_t n_tiles, const int32_t* __restrict__ ray_order,
+                                                                          uint32_t tpr) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  typename Ops<T>::v8 breg[NS];
+  uint32_t k = blockIdx.x, k_end = n_tiles, step = gridDim.x;  // fewer than 8 workgroups: a plain stride over the ordered tiles
+  // Workgroups with equal blockIdx.x % 8 share an XCD, and so an L2: group x walks the x-th contiguous eighth of the ordered tiles, gridDim.x / 8
+  // members striding inside it, so that each L2 holds the rows of its own range of frame times, however many frames the batch spans.  Placement is
+  // affinity only: the eight ranges tile [0, n_tiles) whatever runs where.  (The launcher makes the grid a multiple of 8; workgroups past the last
+  // whole eight would have no place.)  Against a plain stride over the whole list, where every L2 sees the same one or two frame times: 274.5-274.8
+  // against 276.3-276.8 us alone at the preset, 0.836 against 0.845 GB fetched (profiles/r23_fwd_order_INDEX.md).
+  if (gridDim.x >= 8) {
+    const uint32_t x = blockIdx.x & 7;
+    step = gridDim.x >> 3;
+    if ((blockIdx.x >> 3) >= step) return;
+    k = (uint32_t)((uint64_t)x * n_tiles >> 3) + (blockIdx.x >> 3);
+    k_end = (uint32_t)((uint64_t)(x + 1) * n_tiles >> 3);
+  }
+  field_stage_weights<T, NS, VD>(a, smem, breg);
+  for (; k < k_end; k += step) {
+    const uint32_t r = k / tpr, sub = k - r * tpr;
+    field_tile<T, NS, KEEP, VD>(
+        a, ((int64_t)ray_order[r] * tpr + sub) * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
+        [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
+  }
+}
+
 int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N, const snerf_mlp_desc* sd, const snerf_mlp_desc* cd,
                    int max_scales) {
   SNERF_REQUIRE(d && c && sd && cd, "kplanes_field: null descriptor");
@@ -52,28 +85,35 @@ int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N
 }
 
 template <typename T, int NS, int KEEP, bool VD>
-static int launch_field_fwd_k(const FieldArgs& a, hipStream_t st) {
+static int launch_field_fwd_k(const FieldArgs& a, const int32_t* ray_order, hipStream_t st) {
   using P = PlanFF<NS>;
   const int64_t n_tiles = (a.N + FF_TS - 1) / FF_TS;
   int per_cu = (int)(LDS_LIMIT / P::BYTES);
   per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // 125 VGPRs: two 8-wave workgroups per CU
   int64_t grid = 256 * per_cu;
   if (grid > n_tiles) grid = n_tiles;
-  auto k = field_fwd_kernel<T, NS, KEEP, VD>;
-  SNERF_ALLOW_LDS(k, LDS_LIMIT);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, n_tiles);
+  if (ray_order) {
+    auto k = field_fwd_ordered_kernel<T, NS, KEEP, VD>;
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
+    if (grid >= 8) grid &= ~(int64_t)7;  // whole eights: one member count for the eight groups of the kernel's walk
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, (uint32_t)n_tiles, ray_order, (uint32_t)(a.c.S / FF_TS));
+  } else {
+    auto k = field_fwd_kernel<T, NS, KEEP, VD>;
+    SNERF_ALLOW_LDS(k, LDS_LIMIT);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, n_tiles);
+  }
   SNERF_LAUNCH_CHECK("kplanes_field_fwd");
   return 0;
 }
 template <typename T, int NS, bool VD>
-static int launch_field_fwd_vd(const FieldArgs& a, hipStream_t st) {
-  if (a.feat16 && a.feat32) return launch_field_fwd_k<T, NS, 2, VD>(a, st);
-  if (a.feat16) return launch_field_fwd_k<T, NS, 1, VD>(a, st);
-  return launch_field_fwd_k<T, NS, 0, VD>(a, st);
+static int launch_field_fwd_vd(const FieldArgs& a, const int32_t* ray_order, hipStream_t st) {
+  if (a.feat16 && a.feat32) return launch_field_fwd_k<T, NS, 2, VD>(a, ray_order, st);
+  if (a.feat16) return launch_field_fwd_k<T, NS, 1, VD>(a, ray_order, st);
+  return launch_field_fwd_k<T, NS, 0, VD>(a, ray_order, st);
 }
 template <typename T, int NS>
-static int launch_field_fwd(const FieldArgs& a, hipStream_t st, bool vd) {
-  return vd ? launch_field_fwd_vd<T, NS, true>(a, st) : launch_field_fwd_vd<T, NS, false>(a, st);
+static int launch_field_fwd(const FieldArgs& a, const int32_t* ray_order, hipStream_t st, bool vd) {
+  return vd ? launch_field_fwd_vd<T, NS, true>(a, ray_order, st) : launch_field_fwd_vd<T, NS, false>(a, ray_order, st);
 }
 
 }  // namespace snerf
@@ -87,11 +127,16 @@ extern "C" int snerf_kplanes_field_fwd_supported(const snerf_kplanes_desc* desc,
   return desc && sigma && color && validate_field(desc, &c, 0, sigma, color, 6) == 0 ? 1 : 0;
 }
 
-extern "C" int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
-                                       const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
-                                       float* density, float* rgb, void* feat16, float* h, float* feat32, snerf_stream_t stream) {
+extern "C" int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
+                                               const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
+                                               float* density, float* rgb, void* feat16, float* h, float* feat32, const int32_t* ray_order,
+                                               snerf_stream_t stream) {
   int rc = validate_field(desc, coords, N, sigma, color, 6);
   if (rc) return rc;
+  if (ray_order)
+    SNERF_REQUIRE(coords->mode == 1 && coords->S % FF_TS == 0,
+                  "kplanes_field_fwd_ordered: a ray order needs per-ray coordinates (coords.mode = 1) and S a multiple of %d; got mode=%d S=%d", FF_TS,
+                  coords->mode, coords->S);
   if (N == 0) return 0;
   SNERF_REQUIRE(planes && W_sigma && W_color && density && rgb, "kplanes_field_fwd: null buffer");
   FieldArgs a = {};
@@ -99,5 +144,11 @@ extern "C" int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const flo
   SNERF_REQUIRE((feat16 != nullptr) == (h != nullptr) && (!feat32 || feat16),
                 "kplanes_field_fwd: the training outputs come as a set: feat16 and h together, feat32 only with them");
   a.feat16 = feat16; a.h = h; a.feat32 = feat32;
-  FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, (hipStream_t)stream, color->d_in != FF_GEO);
+  FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, ray_order, (hipStream_t)stream, color->d_in != FF_GEO);
+}
+
+extern "C" int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
+                                       const snerf_mlp_desc* sigma, const float* W_sigma, const snerf_mlp_desc* color, const float* W_color,
+                                       float* density, float* rgb, void* feat16, float* h, float* feat32, snerf_stream_t stream) {
+  return snerf_kplanes_field_fwd_ordered(desc, planes, coords, N, sigma, W_sigma, color, W_color, density, rgb, feat16, h, feat32, nullptr, stream);
 }

@@ -164,6 +164,28 @@ __global__ __launch_bounds__(256) void sort_rays_kernel(const int64_t* __restric
   }
 }
 
+// The permutation that sorts the rays' times ascending, ties by ray index: the same one-workgroup bitonic sort, on 64-bit words (time bits << 32 | ray).
+// Times are non-negative, so their bit patterns order as unsigned integers; whatever the bits are, the low words are the distinct ray indices and the
+// padding word is above every key, so the output is always a permutation of 0..R-1.
+__global__ __launch_bounds__(256) void ray_time_order_kernel(const float* __restrict__ times, int R, int n_pow2, int32_t* __restrict__ order_out) {
+  extern __shared__ uint64_t s_tk[];
+  for (int i = threadIdx.x; i < n_pow2; i += blockDim.x)
+    s_tk[i] = i < R ? (((uint64_t)__float_as_uint(times[i]) << 32) | (uint32_t)i) : ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= n_pow2; k <<= 1)
+    for (int lj = 31 - __clz(k >> 1); lj >= 0; --lj) {  // partner distance j = 2^lj
+      const int j = 1 << lj;
+      for (int t = threadIdx.x; t < n_pow2 / 2; t += blockDim.x) {
+        const int i = ((t >> lj) << (lj + 1)) | (t & (j - 1)), l = i + j;
+        const bool up = (i & k) == 0;
+        const uint64_t a = s_tk[i], b = s_tk[l];
+        if ((a > b) == up) { s_tk[i] = b; s_tk[l] = a; }
+      }
+      __syncthreads();
+    }
+  for (int r = threadIdx.x; r < R; r += blockDim.x) order_out[r] = (int32_t)(uint32_t)s_tk[r];
+}
+
 __global__ void aabb_kernel(const float* __restrict__ o, const float* __restrict__ d, int R, float near_plane, int training, const float* amin3,
                             float* __restrict__ nears, float* __restrict__ fars, float a0, float a1, float a2, float b0, float b1, float b2) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -413,6 +435,18 @@ extern "C" int snerf_sort_rays_by_key(const int64_t* indices_in, const int32_t* 
   hipLaunchKernelGGL(sort_rays_kernel, dim3(1), dim3(256), (size_t)n * sizeof(uint32_t), (hipStream_t)stream, indices_in, image_key, R, n, aux_in, aux_cols,
                      indices_out, aux_out);
   SNERF_LAUNCH_CHECK("sort_rays_by_key");
+  return 0;
+}
+
+extern "C" int snerf_ray_time_order(const float* times, int32_t R, int32_t* order_out, snerf_stream_t stream) {
+  SNERF_REQUIRE(R >= 0 && R <= 16384, "ray_time_order: R=%d (<= 16384: one workgroup sorts in LDS)", R);
+  if (R == 0) return 0;
+  SNERF_REQUIRE(times && order_out, "ray_time_order: null buffer");
+  int n = 2;
+  while (n < R) n <<= 1;
+  SNERF_ALLOW_LDS(ray_time_order_kernel, 16384 * (int)sizeof(uint64_t));  // 128 KB at the largest R
+  hipLaunchKernelGGL(ray_time_order_kernel, dim3(1), dim3(256), (size_t)n * sizeof(uint64_t), (hipStream_t)stream, times, R, n, order_out);
+  SNERF_LAUNCH_CHECK("ray_time_order");
   return 0;
 }
 

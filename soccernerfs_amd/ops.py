@@ -966,6 +966,19 @@ def sort_rays_by_time(indices: torch.Tensor, image_key: torch.Tensor, n_keys: in
     return (out, aux_out.view(aux.shape)) if aux is not None else out
 
 
+def ray_time_order(times: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> int32 [R]: the permutation that sorts the rays' times ascending, ties by ray index (snerf_ray_time_order; R <= 16384).  The batch stays as
+    drawn: the order is what snerf_kplanes_field_fwd_ordered walks its tiles in.  out: a caller-owned int32 buffer of at least R elements."""
+    times = _f32c(times, "times").reshape(-1)
+    R = times.numel()
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=times.device)
+    if not out.is_cuda or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < R:
+        raise RuntimeError("ray_time_order: out must be a contiguous int32 HIP tensor of at least R elements")
+    _lib.check(_lib.lib().snerf_ray_time_order(_ptr(times), R, _ptr(out), _stream()), "ray_time_order")
+    return out[:R]
+
+
 def sample_pixels_uniform(u: torch.Tensor, num_images: int, height: int, width: int, images: Optional[torch.Tensor] = None):
     """PixelSampler.sample_method's uniform draw (pixel_samplers.py:74-77) from u = rand(R,3), fused with the image gather of
     collate_image_dataset_batch (:111-123) when the uint8 image cache [M,H,W,3] is given.  Returns (indices int64 [R,3], target fp32 [R,3] | None)."""

@@ -138,6 +138,12 @@ class KPlanesTrainConfig:
     # untraced step, but the sort under the HBM-bound sweep takes 0.3-0.7 ms and stretches the sweep from 0.82 to 0.97 ms -- steady state 2.03 / 2.07 ms
     # with it against 1.98 / 2.01 without (two runs each, one box; profiles/r05_step_offsets_early_sort.txt).
     sort_before_field_fwd: bool = False
+    # The fused field forward walks its 32-sample tiles in order of the rays' frame time (snerf_ray_time_order on the main stream right after the rays
+    # arrive, so under the previous step's sweep; snerf_kplanes_field_fwd_ordered): the workgroups resident at one moment then read the same few texel
+    # rows of the XT / YT / ZT planes, which stay in L2.  Only that kernel's walk changes: its outputs are bit-identical, and the proposal kernels, the
+    # sort, pass B and the MLP backwards see the batch as drawn (ordering the whole batch, bench.py --time-sorted-rays, lost on those: DESIGN 4.1).
+    # Needs the fused forward and a multiple of 32 nerf samples per ray; otherwise the unordered kernel runs.  profiles/r23_fwd_order_INDEX.md.
+    field_fwd_time_order: bool = True
     # Round 5 (A-B, off): pass B and the optimiser sweep of the field planes PIPELINED by scale (single GPU, inside train_step).  Pass B scatters one part
     # of the scales first; the sweep of those planes then starts on the idle "sort" stream while pass B goes on with the other part on the sweep's stream,
     # whose planes are swept behind it.  "coarse_first": scales 0..n-2, then the finest (~72 % of the floats at the preset); "fine_first": the finest scale
@@ -312,6 +318,9 @@ class KPlanesTrainer(FusedStep):
         if self.fused_field:  # the forward's operand-typed feature tile, kept for the unfused backward (snerf_mlp_bwd_x16)
             dt16 = torch.bfloat16 if self.sigma_net.desc.operands == 1 else torch.float16
             self.buf["feat16"] = torch.empty(R * self.S[2], self.field_planes.out_dim, dtype=dt16, device=self.dev)
+        # plain attribute, so that A-B tools can flip it between steps; the order buffer exists either way (train_step allocates nothing)
+        self.field_fwd_time_order = bool(cfg.field_fwd_time_order and self.fused_field and self.S[2] % 32 == 0 and R <= 16384)
+        self._ray_order = torch.zeros(R, dtype=torch.int32, device=self.dev)
         self.quotient_epilogue = bool(cfg.quotient_epilogue and self.quotient_scatter and self.fused_field and self.sigma_net.desc.operands == 1
                                       and self.sigma_net.desc.hidden == 128 and self.sigma_net.desc.n_hidden == 1)
         if cfg.ray_gradients:
@@ -461,6 +470,9 @@ class KPlanesTrainer(FusedStep):
             if rng["bg"].numel() != 3 * R or any(u.shape[0] != R for u in rng["u"]) or rng["t_rand"].shape[0] != R:
                 raise RuntimeError("rng draws must have one row per ray")
         o, d, t = rays["origins"], rays["directions"], rays["times"].reshape(-1)
+        if self.field_fwd_time_order:  # first on the main stream: done long before the field forward, under the previous step's sweep
+            with self._span("ray_time_order"):
+                _lib.check(self.lib.snerf_ray_time_order(self._p(t), R, self._p(self._ray_order), self._st), "ray_time_order")
         if "nears" not in rays:
             rays["nears"], rays["fars"] = ops.aabb_collide(o, d, self.aabb, cfg.near_plane, training)
         else:
@@ -500,12 +512,13 @@ class KPlanesTrainer(FusedStep):
                 self._qg_step = bool(self._fwd_fused and self.quotient_epilogue and will_sort)
                 if self._fwd_fused:
                     with self._span("kplanes_field_fwd"):
-                        _lib.check(self.lib.snerf_kplanes_field_fwd(C.byref(self._desc_field), self._p(self.field_planes.planes), C.byref(co), C.c_int64(N),
-                                                                    C.byref(self.sigma_net.desc), self._p(self.sigma_net.params), C.byref(self.color_net.desc),
-                                                                    self._p(self.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]),
-                                                                    self._p(b["feat16"]) if keep else None, self._p(b["h"]) if keep else None,
-                                                                    self._p(b["feat"]) if keep and self.quotient_scatter and not self._qg_step else None, self._st),
-                                   "kplanes_field_fwd")
+                        _lib.check(self.lib.snerf_kplanes_field_fwd_ordered(
+                            C.byref(self._desc_field), self._p(self.field_planes.planes), C.byref(co), C.c_int64(N),
+                            C.byref(self.sigma_net.desc), self._p(self.sigma_net.params), C.byref(self.color_net.desc),
+                            self._p(self.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]),
+                            self._p(b["feat16"]) if keep else None, self._p(b["h"]) if keep else None,
+                            self._p(b["feat"]) if keep and self.quotient_scatter and not self._qg_step else None,
+                            self._p(self._ray_order) if self.field_fwd_time_order else None, self._st), "kplanes_field_fwd")
                 else:
                     self._gather(self._desc_field, self.field_planes.planes, co, N, b["feat"])
                 if will_sort and not sort_early:

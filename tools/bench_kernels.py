@@ -50,10 +50,56 @@ def bench_sort(dev, R=4096, S=64, n_times=34):
         print(f"sample sort alone, {name}: N = {pts.shape[0]}, {ms_sort * 1e3:.1f} us ({ss.hist.numel() * 4 / 1e6:.1f} MB workspace)")
 
 
+def bench_field_fwd(dev, R=4096, repeats=5, iters=50):
+    """field_fwd_kernel alone on a batch of the benchmark's own data (bench.py's cameras and frame times, the preset's trainer after a few steps), as
+    a training step launches it (16-bit feature tile and sigma_net outputs kept): in the drawn order and, where the library has it, with its tiles
+    walked in order of frame time (snerf_kplanes_field_fwd_ordered).  `repeats` alternating rounds of `iters` launches each; every round is printed,
+    so the spread of repeated alone runs stands beside the difference.  --iters / --repeats: a short run for a counter pass."""
+    import ctypes as C
+    from soccernerfs_amd import _lib, synthetic
+    from soccernerfs_amd.trainer import KPlanesTrainConfig, KPlanesTrainer
+
+    torch.manual_seed(20231029)
+    L = _lib.lib()
+    tr = KPlanesTrainer(KPlanesTrainConfig(), R, dev)
+    cams = synthetic.make_cameras(20, 960, 540)
+    data = synthetic.render_dataset(cams, synthetic.frame_times(100, 3), list(range(19)), dev, chunk_rows=540)
+    M, H, W = data["images"].shape[:3]
+    for _ in range(3):
+        idx, target = ops.sample_pixels_uniform(torch.rand(R, 3, device=dev), M, H, W, data["images"])
+        rays = ops.generate_rays(idx, data["fx"], data["fy"], data["cx"], data["cy"], data["c2w"], data["times"], aabb=tr.aabb, near_plane=tr.cfg.near_plane,
+                                 training=True)
+        tr.train_step(rays, target)
+    tr.synchronize()
+    b, co, N = tr.buf, tr._coords[2], R * tr.S[2]
+    P = lambda t: C.c_void_p(t.data_ptr())
+    head = (C.byref(tr._desc_field), P(tr.field_planes.planes), C.byref(co), C.c_int64(N), C.byref(tr.sigma_net.desc), P(tr.sigma_net.params),
+            C.byref(tr.color_net.desc), P(tr.color_net.params), P(b["dens"][2]), P(b["rgb"]), P(b["feat16"]), P(b["h"]), None)
+    variants = {"drawn order": lambda: _lib.check(L.snerf_kplanes_field_fwd(*head, ops._stream()), "field_fwd")}
+    if hasattr(L, "snerf_kplanes_field_fwd_ordered"):
+        order = ops.ray_time_order(tr.rays["times"])
+        variants["time order"] = lambda: _lib.check(L.snerf_kplanes_field_fwd_ordered(*head, P(order), ops._stream()), "field_fwd_ordered")
+    n_times = int(torch.unique(tr.rays["times"]).numel())
+    print(f"field forward alone: R = {R}, N = {N}, {n_times} distinct frame times in the batch, {iters} launches per figure")
+    res = {k: [] for k in variants}
+    for _ in range(repeats):
+        for k, fn in variants.items():
+            res[k].append(timeit(fn, iters=iters, warm=3) * 1e3)
+    for k, v in res.items():
+        s = sorted(v)
+        print(f"  {k:12s} us: " + " ".join(f"{x:7.1f}" for x in v) + f"   median {s[len(s) // 2]:.1f}  min {s[0]:.1f}  max {s[-1]:.1f}")
+
+
+def _int_flag(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
 def main():
     dev = torch.device("cuda:0")
     if "--sort" in sys.argv[1:]:  # the sort alone, nothing else
         return bench_sort(dev)
+    if "--field-fwd" in sys.argv[1:]:  # the fused field forward alone, nothing else
+        return bench_field_fwd(dev, repeats=_int_flag("--repeats", 5), iters=_int_flag("--iters", 50))
     R = 4096
     res = {}
     # main field: 5 scales, C=32

@@ -77,10 +77,12 @@ typedef struct {
   int32_t S;             /* samples per ray (mode 1) */
   int32_t rescale;       /* mode 1: 1 = map [0,1] -> [-1,1] */
   int32_t _pad;
-  const float* pts;      /* mode 0: [N,4] */
+  const float* pts;      /* mode 0: [N,4]; [N,3] with a 3-coordinate descriptor */
   const float* origins;  /* mode 1: [R,3] */
   const float* dirs;     /* mode 1: [R,3] */
-  const float* times;    /* mode 1: [R] */
+  const float* times;    /* mode 1: [R].  Read only through a 4-coordinate descriptor: with n_coords == 3 (a static scene, or the space
+                          * planes of a set whose time planes are frozen) no kernel reads it and it may be NULL; with n_coords == 4 a
+                          * NULL is refused on the host by every entry point, before anything is launched. */
   const float* ebins;    /* mode 1: [R,S+1] euclidean bin edges */
   float aabb_min[3];
   float aabb_max[3];
@@ -271,7 +273,8 @@ int snerf_mlp_bwd_fx(const snerf_mlp_desc* desc, const float* W, const float* X,
  * Fused K-Planes field forward = KPlanesField.get_density + get_outputs (NS/fields/kplanes_field.py:275-358) in one kernel: plane gather
  * (interpolate_kplanes :77-126) -> sigma_net (32 n_scales -> 128 -> 16, :249-261) -> density = trunc_exp(column 15) (:308-311) and
  * color_net on the 15 geometry features (15 -> 64 -> 64 -> 3 Sigmoid, :263-273, disable_viewing_dependent) -> rgb.  The features, the
- * 16 sigma_net outputs and every MLP activation stay on chip.  Built for 4-D plane sets with C = 32, concatenated scales (<= 6), the two
+ * 16 sigma_net outputs and every MLP activation stay on chip.  Built for plane sets of four coordinates (six planes per scale) or three (a
+ * static scene: XY, XZ, YZ; also the three-plane view of a four-coordinate set whose time planes are frozen) with C = 32, concatenated scales (<= 6), the two
  * net shapes above and 16-bit MFMA operands (snerf_mlp_desc.operands = 1 bf16 / 2 fp16, both nets alike): snerf_kplanes_field_fwd_supported
  * tells; the exact-fp32 path composes snerf_kplanes_gather_fwd + snerf_mlp_fwd.  Results are bit-identical to that composition run with the
  * same 16-bit operands.  The backward runs unfused on what this kernel leaves behind (snerf_mlp_bwd, snerf_mlp_bwd_x16, the sorted scatter);
@@ -293,7 +296,8 @@ int snerf_kplanes_field_fwd(const snerf_kplanes_desc* desc, const float* planes,
  * walk changes: every sample's outputs land in that sample's own rows, so all outputs equal snerf_kplanes_field_fwd's bit for bit, and every
  * other kernel of the step keeps seeing the batch in the order it was drawn.
  *   ray_order == NULL: snerf_kplanes_field_fwd exactly.
- *   ray_order != NULL: needs coords.mode == 1 and S % 32 == 0 (a tile is then 32 samples of one ray); anything else is an argument error.
+ *   ray_order != NULL: needs coords.mode == 1, S % 32 == 0 (a tile is then 32 samples of one ray) and a 4-coordinate descriptor (the walk exists
+ *   for the time planes' rows; three coordinates take ray_order == NULL); anything else is an argument error.
  * DEVICE DATA: the kernel does not validate the order's contents; it must be a permutation of 0..R-1 (an entry outside that range makes the
  * kernel read and write out of bounds).  The trainer passes what snerf_ray_time_order wrote. */
 int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N,
@@ -309,7 +313,8 @@ int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, const float*
  * (NS/model_components/renderers.py:58-140, :197-223, :226-287).  = snerf_kplanes_field_fwd -> snerf_weights_fwd -> snerf_render_fwd(training = 0,
  * bg_mode = 1), bit for bit when transmittance_cutoff = 0; per-sample density and colour stay on chip (a workgroup owns a whole ray).
  *   coords: mode 1 (per-ray origins / dirs / times + euclidean bin edges [R, S+1]); S a multiple of 32, <= 320; the net shapes and operand types
- *   of snerf_kplanes_field_fwd (1-6 scales, plain and view-dependent colour net).  snerf_kplanes_field_render_supported tells.
+ *   of snerf_kplanes_field_fwd (1-6 scales, six or three planes per scale, plain and view-dependent colour net; coords.times may be NULL with three
+ *   coordinates).  snerf_kplanes_field_render_supported tells.
  *   transmittance_cutoff > 0: early ray termination (not in the reference).  Once exp(-sum sigma delta) over a ray's evaluated 32-sample tiles drops
  *   below the cutoff its remaining tiles are skipped: their samples count as zero density and the background is the last evaluated sample's colour;
  *   |rgb error| and |accumulation error| <= cutoff.  0 = never, the exact path.
@@ -348,7 +353,8 @@ int snerf_kplanes_color_bwd_vd_ws(const snerf_mlp_desc* desc, const float* W, co
 
 /* ------------------------------------------------------------------------------------------------
  * Fused proposal density = KPlanesDensityField.get_density (NS/fields/kplanes_field.py:410-460) as ProposalNetworkSampler calls it per level
- * (NS/model_components/ray_samplers.py:559-600) in one kernel (ABI 11): plane gather (one scale of six C = 8 planes) -> sigma_net 8 -> 64 -> 1
+ * (NS/model_components/ray_samplers.py:559-600) in one kernel (ABI 11): plane gather (one scale of six C = 8 planes, or of three: a 3-coordinate
+ * descriptor, whose coords.times may be NULL) -> sigma_net 8 -> 64 -> 1
  * (16-bit MFMA operands) -> density = trunc_exp(.).  Bit-identical to snerf_kplanes_gather_fwd + snerf_mlp_fwd (aux = trunc_exp) with the same
  * operands.  feat (optional, NULL = not written): the [N,8] fp32 features, which the unfused backward kernels of a step that updates the
  * proposal networks read (snerf_mlp_bwd, snerf_kplanes_gather_bwd).

@@ -20,17 +20,7 @@
 
 namespace snerf {
 
-template <typename T, int NS, int KEEP = 0, bool VD = false>
-__global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, int64_t n_tiles) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* smem = reinterpret_cast<T*>(smem_raw);
-  typename Ops<T>::v8 breg[NS];
-  field_stage_weights<T, NS, VD>(a, smem, breg);
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    field_tile<T, NS, KEEP, VD>(
-        a, tile * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
-        [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
-}
+// field_fwd_kernel itself is defined in field_fused_common.hpp (a template over the plane count as well: field_fused_static.hip builds NP = 3).
 
 // The same tiles walked in the order of a ray permutation (snerf_kplanes_field_fwd_ordered: coords.mode = 1 and S % 32 == 0, so a tile is 32 samples
 // of ONE ray): with tpr = S / 32, tile k of the walk is sub-tile k % tpr of ray ray_order[k / tpr].  All samples of a ray share t, so with the rays in
@@ -68,8 +58,9 @@ __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_ordered_kernel(FieldA
 int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N, const snerf_mlp_desc* sd, const snerf_mlp_desc* cd,
                    int max_scales) {
   SNERF_REQUIRE(d && c && sd && cd, "kplanes_field: null descriptor");
-  SNERF_REQUIRE(d->C == 32 && d->n_coords == 4 && d->concat == 1 && d->n_scales >= 1 && d->n_scales <= max_scales,
-                "kplanes_field: the fused kernels are built for 4-D planes, C = 32, concatenated scales (<= %d); got C=%d coords=%d concat=%d scales=%d",
+  SNERF_REQUIRE(d->C == 32 && (d->n_coords == 4 || d->n_coords == 3) && d->concat == 1 && d->n_scales >= 1 && d->n_scales <= max_scales,
+                "kplanes_field: the fused kernels are built for six or three planes per scale (4 / 3 coordinates), C = 32, concatenated scales (<= %d); "
+                "got C=%d coords=%d concat=%d scales=%d",
                 max_scales, d->C, d->n_coords, d->concat, d->n_scales);
   SNERF_REQUIRE(sd->d_in == 32 * d->n_scales && sd->hidden == FF_H && sd->n_hidden == 1 && sd->d_out == 16 && sd->hidden_act == 1 && sd->out_act == 0,
                 "kplanes_field: sigma_net must be %d -> 128 (ReLU) -> 16", 32 * d->n_scales);
@@ -81,6 +72,10 @@ int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N
   SNERF_REQUIRE(c->mode == 0 || c->mode == 1, "kplanes_field: coords.mode=%d", c->mode);
   if (c->mode == 1) SNERF_REQUIRE(c->S >= 1 && N % c->S == 0, "kplanes_field: N=%lld not a multiple of S=%d", (long long)N, c->S);
   if (cd->d_in != FF_GEO && N > 0) SNERF_REQUIRE(c->mode == 1, "kplanes_field: the view-dependent colour net reads per-ray directions (coords.mode = 1)");
+  // the kernels dereference these: a static scene (three coordinates) has no times, every other ray buffer and a 4-coordinate descriptor's times must be there
+  if (N > 0)
+    SNERF_REQUIRE(c->mode == 0 ? c->pts != nullptr : ray_coords_complete(c, d->n_coords),
+                  "kplanes_field: incomplete coordinates (pts in mode 0; origins / dirs / ebins and, with four coordinates, times in mode 1)");
   return 0;
 }
 
@@ -88,17 +83,14 @@ template <typename T, int NS, int KEEP, bool VD>
 static int launch_field_fwd_k(const FieldArgs& a, const int32_t* ray_order, hipStream_t st) {
   using P = PlanFF<NS>;
   const int64_t n_tiles = (a.N + FF_TS - 1) / FF_TS;
-  int per_cu = (int)(LDS_LIMIT / P::BYTES);
-  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // 125 VGPRs: two 8-wave workgroups per CU
-  int64_t grid = 256 * per_cu;
-  if (grid > n_tiles) grid = n_tiles;
+  int64_t grid = field_fwd_grid<NS>(n_tiles);
   if (ray_order) {
     auto k = field_fwd_ordered_kernel<T, NS, KEEP, VD>;
     SNERF_ALLOW_LDS(k, LDS_LIMIT);
     if (grid >= 8) grid &= ~(int64_t)7;  // whole eights: one member count for the eight groups of the kernel's walk
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, (uint32_t)n_tiles, ray_order, (uint32_t)(a.c.S / FF_TS));
   } else {
-    auto k = field_fwd_kernel<T, NS, KEEP, VD>;
+    auto k = field_fwd_kernel<T, NS, KEEP, VD, 6>;
     SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), P::BYTES, st, a, n_tiles);
   }
@@ -137,6 +129,8 @@ extern "C" int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, c
     SNERF_REQUIRE(coords->mode == 1 && coords->S % FF_TS == 0,
                   "kplanes_field_fwd_ordered: a ray order needs per-ray coordinates (coords.mode = 1) and S a multiple of %d; got mode=%d S=%d", FF_TS,
                   coords->mode, coords->S);
+  if (ray_order)  // the frame-time walk exists for the time planes' rows
+    SNERF_REQUIRE(desc->n_coords == 4, "kplanes_field_fwd_ordered: a ray order needs a 4-coordinate descriptor; got coords=%d", desc->n_coords);
   if (N == 0) return 0;
   SNERF_REQUIRE(planes && W_sigma && W_color && density && rgb, "kplanes_field_fwd: null buffer");
   FieldArgs a = {};
@@ -144,6 +138,7 @@ extern "C" int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, c
   SNERF_REQUIRE((feat16 != nullptr) == (h != nullptr) && (!feat32 || feat16),
                 "kplanes_field_fwd: the training outputs come as a set: feat16 and h together, feat32 only with them");
   a.feat16 = feat16; a.h = h; a.feat32 = feat32;
+  if (desc->n_coords == 3) return launch_field_fwd_static(a, sigma->operands, (hipStream_t)stream, color->d_in != FF_GEO);
   FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, ray_order, (hipStream_t)stream, color->d_in != FF_GEO);
 }
 

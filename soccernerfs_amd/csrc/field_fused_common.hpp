@@ -50,16 +50,18 @@ struct PlanFF {
   static constexpr size_t BYTES = (size_t)TOTAL * 2;
 };
 
-// features of one sample for this lane's 4 channels and scale s: product over the six planes (interpolate_kplanes, kplanes_field.py:77-126)
+// features of one sample for this lane's 4 channels and scale s: product over the NP planes -- six, or the three space planes of a static scene /
+// of frozen time planes (interpolate_kplanes, kplanes_field.py:77-126; :95-99)
+template <int NP = 6>
 __device__ __forceinline__ float4 scale_features(const snerf_kplanes_desc& d, const float* __restrict__ planes, const float p[4], int s, int cg,
-                                                 float4 (*v_out)[6] = nullptr) {
+                                                 float4 (*v_out)[NP] = nullptr) {
   AxisTap tap[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) tap[k] = axis_tap(p[k], d.res[s][k] > 0 ? d.res[s][k] : 1);
   float4 prod = make_float4(1.f, 1.f, 1.f, 1.f);
 #pragma unroll
-  for (int q = 0; q < 6; ++q) {
-    const float4 v = plane_sample<32>(planes + d.off[s][q], d.res[s][pair_a<6>(q)], tap[pair_a<6>(q)], tap[pair_b<6>(q)], cg);
+  for (int q = 0; q < NP; ++q) {
+    const float4 v = plane_sample<32>(planes + d.off[s][q], d.res[s][pair_a<NP>(q)], tap[pair_a<NP>(q)], tap[pair_b<NP>(q)], cg);
     if (v_out) (*v_out)[q] = v;
     prod = f4_mul(prod, v);
   }
@@ -85,7 +87,7 @@ __device__ __forceinline__ void load_breg(const float* __restrict__ W0, int wave
 }
 
 // gather phase: 16 lanes per sample = (4-channel group cg) x (scale parity sg); rounds the features into the A-operand image XS
-template <typename T, int NS, bool F32OUT = false>
+template <typename T, int NS, bool F32OUT = false, int NP = 6>
 __device__ __forceinline__ void gather_tile(const FieldArgs& a, int64_t n0, T* XS) {
   using P = PlanFF<NS>;
   // waves 0-3 take the even scales, waves 4-7 the odd ones: the scale index is wave-uniform, so the descriptor reads stay scalar
@@ -93,11 +95,11 @@ __device__ __forceinline__ void gather_tile(const FieldArgs& a, int64_t n0, T* X
   const int64_t n = n0 + sample;
   float p[4];
   const bool live = n < a.N;
-  if (live) load_coords<6>(a.c, n, p);
+  if (live) load_coords<NP>(a.c, n, p);
 #pragma unroll 1  // one scale's 24 texel reads in flight at a time: unrolled, the three scales' loads cost ~160 VGPRs and the occupancy the kernel lives on
   for (int s = sg; s < NS; s += 2) {
     float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) f = scale_features(a.d, a.planes, p, s, cg);
+    if (live) f = scale_features<NP>(a.d, a.planes, p, s, cg);
     const typename Ops<T>::v4 t = {Ops<T>::cvt(f.x), Ops<T>::cvt(f.y), Ops<T>::cvt(f.z), Ops<T>::cvt(f.w)};
     *reinterpret_cast<typename Ops<T>::v4*>(XS + sample * P::LK0 + s * 32 + cg * 4) = t;
     if constexpr (F32OUT)
@@ -146,7 +148,8 @@ __device__ __forceinline__ void field_stage_weights(const FieldArgs& a, T* smem,
 // rgb(row in tile, n, channel, value) from waves 0-1 after the colour net -- so a caller decides where density and colour live.
 // KEEP: what a training step leaves behind for its backward -- 0 nothing (eval), 1 the 16-bit feature tile + the sigma_net outputs,
 // 2 those + the fp32 features (quotient scatter).  Compile-time: as run-time pointer tests these cost every variant registers.
-template <typename T, int NS, int KEEP, bool VD, typename DensSink, typename RgbSink>
+// NP: planes per scale, 6 or 3 (a 3-coordinate descriptor); a template parameter too, so that the six-plane tile is the code it was.
+template <typename T, int NS, int KEEP, bool VD, int NP = 6, typename DensSink, typename RgbSink>
 __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* smem, const typename Ops<T>::v8 (&breg)[NS], DensSink&& dens_sink,
                                            RgbSink&& rgb_sink) {
   using P = PlanFF<NS>;
@@ -155,7 +158,7 @@ __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* sm
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   T *XS = smem + P::XS, *A1 = smem + P::A1, *CX = smem + P::CX, *CA1 = smem + P::XS, *CA2 = smem + P::XS + FF_TS * P::LKC;
   __syncthreads();  // weights staged / the previous tile's colour layers have read CA1, CA2 (= XS)
-  gather_tile<T, NS, KEEP == 2>(a, n0, XS);
+  gather_tile<T, NS, KEEP == 2, NP>(a, n0, XS);
   if constexpr (VD) {  // one SH coefficient per thread: 32 samples x 16 (the previous tile's colour layer 0 read CX before the loop-top barrier)
     const int sample = threadIdx.x >> 4, k = threadIdx.x & 15;
     const int64_t n = n0 + sample;
@@ -217,8 +220,34 @@ __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* sm
   }
 }
 
+// The forward kernel (field_fused.hip describes it): a persistent workgroup strides over the tiles; density and colour go to HBM.  NP = 6 is
+// instantiated by field_fused.hip, NP = 3 (a 3-coordinate descriptor) by field_fused_static.hip.
+template <typename T, int NS, int KEEP = 0, bool VD = false, int NP = 6>
+__global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, int64_t n_tiles) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  typename Ops<T>::v8 breg[NS];
+  field_stage_weights<T, NS, VD>(a, smem, breg);
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    field_tile<T, NS, KEEP, VD, NP>(
+        a, tile * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
+        [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
+}
+
+// grid of the persistent forward: two 8-wave workgroups per CU where the LDS plan allows (125 VGPRs)
+template <int NS>
+inline int64_t field_fwd_grid(int64_t n_tiles) {
+  int per_cu = (int)(LDS_LIMIT / PlanFF<NS>::BYTES);
+  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
+  const int64_t grid = 256 * per_cu;
+  return grid > n_tiles ? n_tiles : grid;
+}
+
 // the shapes the fused field kernels are built for (snerf_kplanes_field_fwd_supported)
 int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N, const snerf_mlp_desc* sd, const snerf_mlp_desc* cd, int max_scales = 6);
+
+// the unordered forward for a 3-coordinate descriptor (field_fused_static.hip: the NP = 3 instantiations in a translation unit of their own)
+int launch_field_fwd_static(const FieldArgs& a, int operands, hipStream_t st, bool vd);
 
 #define FF_DISPATCH(FN, operands, ns, ...)                                                   \
   do {                                                                                       \

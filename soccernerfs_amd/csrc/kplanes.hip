@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_kernel(snerf_kplanes_d
         const int64_t n = n0 + (i0 + u < cnt ? i0 + u : cnt - 1);
         float p[4];
         if (c.mode == 1) {
-          load_coords_ray(c, ray, sir, p);
+          load_coords_ray<NP>(c, ray, sir, p);
           if (i0 + u + 1 < cnt && ++sir == c.S) { sir = 0; ++ray; }
         } else {
           load_coords<NP>(c, n, p);
@@ -182,7 +182,7 @@ static int validate(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t 
     SNERF_REQUIRE(c->pts || N == 0, "kplanes: pts is null");
   } else if (c->mode == 1) {
     SNERF_REQUIRE(c->S >= 1 && N % c->S == 0, "kplanes: N=%lld not a multiple of S=%d", (long long)N, c->S);
-    SNERF_REQUIRE((c->origins && c->dirs && c->times && c->ebins) || N == 0, "kplanes: null ray buffers");
+    SNERF_REQUIRE(ray_coords_complete(c, d->n_coords) || N == 0, "kplanes: null ray buffers (times may be null only with three coordinates)");
   } else {
     SNERF_REQUIRE(false, "kplanes: coords.mode=%d unsupported", c->mode);
   }

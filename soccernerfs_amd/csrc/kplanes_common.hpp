@@ -30,7 +30,9 @@ __device__ __forceinline__ AxisTap tap_from_pix(float fx, int size) {
 }
 __device__ __forceinline__ AxisTap axis_tap(float x, int size) { return tap_from_pix(axis_pix(x, size), size); }
 
-// coordinate of sample s of ray r (snerf_coords mode 1: positions derived from rays + euclidean bin edges)
+// coordinate of sample s of ray r (snerf_coords mode 1: positions derived from rays + euclidean bin edges).  NP = 3 (static scene): there is no
+// time axis and c.times, which may be null then, is never read.
+template <int NP = 6>
 __device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r, int s, float p[4]) {
   const float* eb = c.ebins + r * (c.S + 1) + s;
   float mid = eb[0] + eb[1];
@@ -40,8 +42,12 @@ __device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r
     float q = (pos - c.aabb_min[k]) / (c.aabb_max[k] - c.aabb_min[k]);
     p[k] = c.rescale ? q * 2.f - 1.f : q;
   }
-  p[3] = c.times[r] * 2.f - 1.f;
+  if constexpr (NP == 6) p[3] = c.times[r] * 2.f - 1.f;
+  else p[3] = 0.f;
 }
+
+// host: the ray buffers of mode-1 coordinates are all there.  A 4-coordinate descriptor needs the rays' times; a static scene has none to give.
+inline bool ray_coords_complete(const snerf_coords* c, int n_coords) { return c->origins && c->dirs && c->ebins && (c->times || n_coords == 3); }
 
 // coordinate of sample n along x,y,z,t in grid_sample's [-1,1] convention
 template <int NP>
@@ -56,7 +62,7 @@ __device__ __forceinline__ void load_coords(const snerf_coords& c, int64_t n, fl
   } else {
     int64_t r = n / c.S;  // a 64-bit software division (~100 instructions): loops over consecutive samples step (r, s) themselves
     int s = (int)(n - r * c.S);
-    load_coords_ray(c, r, s, p);
+    load_coords_ray<NP>(c, r, s, p);
   }
 }
 

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kp
     if (active) {
       float p[4];
       if (c.mode == 1) {
-        load_coords_ray(c, owner, i, p);
+        load_coords_ray<NP>(c, owner, i, p);
         const float* eb = c.ebins + owner * (c.S + 1) + i;
         tmid = (eb[0] + eb[1]) / 2.f;
       } else {
@@ -176,7 +176,8 @@ extern "C" int snerf_kplanes_gather_bwd_coords(const snerf_kplanes_desc* desc, c
   } else if (coords->mode == 1) {
     SNERF_REQUIRE(coords->S >= 1 && N % coords->S == 0, "kplanes_gather_bwd_coords: N=%lld not a multiple of S=%d",
                   (long long)N, coords->S);
-    SNERF_REQUIRE((coords->origins && coords->dirs && coords->times && coords->ebins) || N == 0, "kplanes_gather_bwd_coords: null ray buffers");
+    SNERF_REQUIRE(ray_coords_complete(coords, desc->n_coords) || N == 0,
+                  "kplanes_gather_bwd_coords: null ray buffers (times may be null only with three coordinates)");
   } else {
     SNERF_REQUIRE(false, "kplanes_gather_bwd_coords: coords.mode=%d unsupported", coords->mode);
   }

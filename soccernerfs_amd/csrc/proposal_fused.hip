@@ -43,7 +43,8 @@ struct DensityArgs {
   float* feat;         // optional [N,8] fp32: the features, for the proposal net's / planes' backward kernels
 };
 
-template <typename T>
+// NP: planes of the level, 6 or 3 (a static scene, or the space planes of frozen time planes); NP = 3 never reads coords.times
+template <typename T, int NP = 6>
 __global__ __launch_bounds__(PF_NW * 64) void density_fwd_kernel(DensityArgs a, int64_t n_tiles) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -68,21 +69,25 @@ __global__ __launch_bounds__(PF_NW * 64) void density_fwd_kernel(DensityArgs a, 
     if (n < a.N) {
       float p[4];
       if (a.c.mode == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(a.c.pts + n * 4);
-        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+        if constexpr (NP == 6) {
+          const float4 v = *reinterpret_cast<const float4*>(a.c.pts + n * 4);
+          p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+        } else {  // pts is [N,3]
+          p[0] = a.c.pts[n * 3]; p[1] = a.c.pts[n * 3 + 1]; p[2] = a.c.pts[n * 3 + 2]; p[3] = 0.f;
+        }
       } else {
         const uint32_t r = (uint32_t)n / (uint32_t)a.c.S;  // N < 2^31 (checked by the launcher)
-        load_coords_ray(a.c, (int64_t)r, (int)((uint32_t)n - r * (uint32_t)a.c.S), p);
+        load_coords_ray<NP>(a.c, (int64_t)r, (int)((uint32_t)n - r * (uint32_t)a.c.S), p);
       }
       AxisTap tap[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) tap[k] = axis_tap(p[k], res[k]);
-      float2 t[6][4];
+      float2 t[NP][4];
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const AxisTap& tx = tap[pair_a<6>(q)];
-        const AxisTap& ty = tap[pair_b<6>(q)];
-        const int W = d.res[0][pair_a<6>(q)];
+      for (int q = 0; q < NP; ++q) {
+        const AxisTap& tx = tap[pair_a<NP>(q)];
+        const AxisTap& ty = tap[pair_b<NP>(q)];
+        const int W = d.res[0][pair_a<NP>(q)];
         const float* base = a.planes + d.off[0][q] + cg * 2;
         const float* r0 = base + ((int64_t)ty.i0 * W) * PF_C;
         const float* r1 = base + ((int64_t)ty.i1 * W) * PF_C;
@@ -93,8 +98,8 @@ __global__ __launch_bounds__(PF_NW * 64) void density_fwd_kernel(DensityArgs a, 
       }
       float2 pr = make_float2(1.f, 1.f);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const float4 w = tap_weights(tap[pair_a<6>(q)], tap[pair_b<6>(q)]);
+      for (int q = 0; q < NP; ++q) {
+        const float4 w = tap_weights(tap[pair_a<NP>(q)], tap[pair_b<NP>(q)]);
         pr.x *= bilerp4(t[q][0].x, t[q][1].x, t[q][2].x, t[q][3].x, w.x, w.y, w.z, w.w);
         pr.y *= bilerp4(t[q][0].y, t[q][1].y, t[q][2].y, t[q][3].y, w.x, w.y, w.z, w.w);
       }
@@ -134,18 +139,18 @@ __global__ __launch_bounds__(PF_NW * 64) void density_fwd_kernel(DensityArgs a, 
   }
 }
 
-template <typename T>
+template <typename T, int NP>
 static int launch_density(const DensityArgs& a, hipStream_t st) {
   const int64_t n_tiles = (a.N + PF_TS - 1) / PF_TS;
   int64_t grid = 256 * 6;
   if (grid > n_tiles) grid = n_tiles;
-  hipLaunchKernelGGL((density_fwd_kernel<T>), dim3((unsigned)grid), dim3(PF_NW * 64), PlanPF::BYTES, st, a, n_tiles);
+  hipLaunchKernelGGL((density_fwd_kernel<T, NP>), dim3((unsigned)grid), dim3(PF_NW * 64), PlanPF::BYTES, st, a, n_tiles);
   SNERF_LAUNCH_CHECK("kplanes_density_fwd");
   return 0;
 }
 
 static bool density_shape_ok(const snerf_kplanes_desc* d, const snerf_mlp_desc* m) {
-  return d && m && d->C == PF_C && d->n_coords == 4 && d->n_scales == 1 && m->d_in == PF_C && m->hidden == PF_H && m->n_hidden == 1 && m->d_out == 1 &&
+  return d && m && d->C == PF_C && (d->n_coords == 4 || d->n_coords == 3) && d->n_scales == 1 && m->d_in == PF_C && m->hidden == PF_H && m->n_hidden == 1 && m->d_out == 1 &&
          (m->operands == 1 || m->operands == 2) && m->out_act == 0 && (m->hidden_act == 0 || m->hidden_act == 1);
 }
 
@@ -158,16 +163,17 @@ extern "C" int snerf_kplanes_density_fwd_supported(const snerf_kplanes_desc* des
 extern "C" int snerf_kplanes_density_fwd(const snerf_kplanes_desc* desc, const float* planes, const snerf_coords* coords, int64_t N, const snerf_mlp_desc* net,
                                          const float* W, float* density, float* feat, snerf_stream_t stream) {
   SNERF_REQUIRE(desc && coords && net, "kplanes_density_fwd: null descriptor");
-  SNERF_REQUIRE(density_shape_ok(desc, net), "kplanes_density_fwd: built for one scale of six C = 8 planes and the 8 -> 64 -> 1 net with 16-bit operands "
+  SNERF_REQUIRE(density_shape_ok(desc, net), "kplanes_density_fwd: built for one scale of six or three C = 8 planes and the 8 -> 64 -> 1 net with 16-bit operands "
                 "(C=%d n_coords=%d n_scales=%d; net %d -> %d x %d -> %d, operands %d)", desc->C, desc->n_coords, desc->n_scales, net->d_in, net->hidden,
                 net->n_hidden, net->d_out, net->operands);
   SNERF_REQUIRE(N >= 0 && N < (1LL << 31), "kplanes_density_fwd: N=%lld", (long long)N);
   SNERF_REQUIRE(coords->mode == 0 || coords->mode == 1, "kplanes_density_fwd: coords.mode=%d", coords->mode);
   if (N == 0) return 0;
+  SNERF_REQUIRE(coords->mode == 0 ? coords->pts != nullptr : (ray_coords_complete(coords, desc->n_coords) && coords->S > 0),
+                "kplanes_density_fwd: incomplete coordinates (times may be null only with three coordinates)");
   SNERF_REQUIRE(planes && W && density, "kplanes_density_fwd: null buffer");
-  SNERF_REQUIRE(coords->mode == 0 ? coords->pts != nullptr : (coords->origins && coords->dirs && coords->ebins && coords->times && coords->S > 0),
-                "kplanes_density_fwd: incomplete coordinates");
   DensityArgs a = {};
   a.d = *desc; a.planes = planes; a.c = *coords; a.N = N; a.W = W; a.relu = net->hidden_act == 1; a.dens = density; a.feat = feat;
-  return net->operands == 2 ? launch_density<fp16>(a, (hipStream_t)stream) : launch_density<bf16>(a, (hipStream_t)stream);
+  if (desc->n_coords == 3) return net->operands == 2 ? launch_density<fp16, 3>(a, (hipStream_t)stream) : launch_density<bf16, 3>(a, (hipStream_t)stream);
+  return net->operands == 2 ? launch_density<fp16, 6>(a, (hipStream_t)stream) : launch_density<bf16, 6>(a, (hipStream_t)stream);
 }

@@ -12,19 +12,17 @@
 // bin edges [S+1] stay in LDS (7.7 KB at the limit S = 320, beside the ~43 KB of the tile: two workgroups per CU as before); per-sample density
 // and colour never reach HBM.  After the last tile wave 0 runs the per-ray phases of resample_kernel stage 1 (snerf_weights_fwd) and
 // render_fwd_kernel (training = 0, bg_mode = 1) on the LDS-resident values -- the same functions of per_ray_common.hpp -- so the outputs equal
-// the three-kernel chain bit for bit, as ray_train_kernel's equal the training step's five.
+// the three-kernel chain bit for bit, as ray_train_kernel's equal the training step's five.  The kernel is defined in render_eval_common.hpp,
+// a template over the plane count: render_eval_static.hip builds the three-plane form.
 //
 // Early ray termination (transmittance_cutoff > 0): after a tile every wave forms the ray's remaining transmittance T = exp(-sum sigma delta) over
 // the samples evaluated so far (the same LDS values, the same arithmetic: the decision is workgroup-uniform without a broadcast).  If T < cutoff
 // the ray's remaining tiles are not gathered or decoded; their samples count as zero density, and the background is the last evaluated sample's
 // colour.  The weights that are dropped sum to less than T: |rgb error| <= cutoff per channel.  cutoff = 0 never terminates: the exact path.
-#include "field_fused_common.hpp"
-#include "per_ray_common.hpp"
+#include "render_eval_common.hpp"
 #include "raygen_common.hpp"
 
 namespace snerf {
-
-constexpr size_t RAY_LDS_B = sizeof(float) * (MAX_S * 6 + 4);  // a ray's density / prefix sums / colour / bin edges behind the tile's LDS plan
 
 struct FrameRaygenArgs {
   float fx, fy, cx, cy, c2w[12], time;
@@ -91,90 +89,17 @@ __global__ void raygen_frame_cam_kernel(FrameRaygenCamArgs q) {
   aabb_interval(p.o, p.d, a.aabb_min, a.aabb_max, a.near_plane, 0, a.nears[r], a.fars[r]);
 }
 
-struct RayOut {
-  float cutoff;
-  float* rgb_out; float* acc_out; float* depth_median; float* depth_expected;
-  int64_t* median_index; int32_t* samples_done;
-};
-
-// One ray by ONE wavefront from LDS: dd holds the densities of the first `done` samples on entry (the rest count as zero), col the colours,
-// eb the S + 1 euclidean bin edges.  The phases of snerf_weights_fwd and of render_fwd_kernel in eval mode (per_ray_common.hpp), with the
-// wave's own barrier between them.
-__device__ __forceinline__ void composite_ray(float* dd, float* aux, const float* col, const float* eb, int S, int done, int64_t r, const RayOut& o,
-                                              int lane) {
-#pragma clang fp contract(off)
-  ray_weights<WaveSync>(eb, dd, done, dd, aux, dd, nullptr, false, S, lane);  // from here on dd holds the weights
-  wave_lds_publish();
-  const RaySums s = ray_weighted_sums<true>(dd, nullptr, col, done, true, eb, S, lane);
-  const int idx = ray_median_index<WaveSync>(dd, aux, S, lane);
-  if (lane == 0) {
-    float b[3], out[3];
-    ray_background(1, nullptr, r, col + (done - 1) * 3, true, b);  // "last_sample" background: the last EVALUATED sample
-    ray_blend(s, b, true, out);
-    o.rgb_out[r * 3] = out[0]; o.rgb_out[r * 3 + 1] = out[1]; o.rgb_out[r * 3 + 2] = out[2];
-    o.acc_out[r] = s.acc;
-    if (o.median_index) o.median_index[r] = idx;
-    if (o.depth_median) o.depth_median[r] = bin_midpoint(eb, idx);
-    if (o.depth_expected) o.depth_expected[r] = s.dsum / (s.acc + 1e-10f);
-    if (o.samples_done) o.samples_done[r] = done;
-  }
-}
-
-// sum of delta * sigma over the tile's 32 samples, the same value in every lane of every wave
-__device__ __forceinline__ float tile_optical_depth(const float* dens, const float* eb, int lane) {
-#pragma clang fp contract(off)
-  float v = 0.f;
-  if (lane < FF_TS) v = (eb[lane + 1] - eb[lane]) * dens[lane];
-  return wave_sum(v);
-}
-
-template <typename T, int NS, bool VD>
-__global__ __launch_bounds__(FF_NW * 64, 4) void field_render_kernel(FieldArgs a, int R, RayOut o) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* smem = reinterpret_cast<T*>(smem_raw);
-  float* s_dd = reinterpret_cast<float*>(smem_raw + PlanFF<NS>::BYTES);  // [MAX_S] density, then delta * sigma, then the weights
-  float* s_aux = s_dd + MAX_S;                                           // [MAX_S] the two prefix sums
-  float* s_col = s_aux + MAX_S;                                          // [MAX_S, 3]
-  float* s_eb = s_col + MAX_S * 3;                                       // [MAX_S + 1]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int S = a.c.S, n_tiles = S / FF_TS;
-  typename Ops<T>::v8 breg[NS];
-  field_stage_weights<T, NS, VD>(a, smem, breg);
-  for (int ray = blockIdx.x; ray < R; ray += gridDim.x) {
-    // the previous ray's compositing (wave 0) read s_eb: the barrier below is behind it for every wave
-    __syncthreads();
-    for (int i = threadIdx.x; i <= S; i += FF_NW * 64) s_eb[i] = a.c.ebins[(int64_t)ray * (S + 1) + i];
-    float tau = 0.f;
-    int done = S;
-    for (int t = 0; t < n_tiles; ++t) {
-      field_tile<T, NS, 0, VD>(
-          a, (int64_t)ray * S + t * FF_TS, smem, breg, [&](int row, int64_t, float v) { s_dd[t * FF_TS + row] = v; },
-          [&](int row, int64_t, int c, float v) { s_col[(t * FF_TS + row) * 3 + c] = v; });
-      if (o.cutoff > 0.f && t + 1 < n_tiles) {
-        // the tile's densities were published by the barrier behind the sigma_net output layer; s_eb by the tile's first barrier
-        tau += tile_optical_depth(s_dd + t * FF_TS, s_eb + t * FF_TS, lane);
-        if (expf(-tau) < o.cutoff) { done = (t + 1) * FF_TS; break; }  // workgroup-uniform: every wave formed the same tau
-      }
-    }
-    __syncthreads();  // the last tile's colours (waves 0-1) are in LDS
-    if (wave == 0) composite_ray(s_dd, s_aux, s_col, s_eb, S, done, ray, o, lane);
-  }
-}
-
 template <typename T, int NS>
 static int launch_field_render(const FieldArgs& a, int R, const RayOut& o, hipStream_t st, bool vd) {
   using P = PlanFF<NS>;
   constexpr size_t BYTES = P::BYTES + RAY_LDS_B;
-  int per_cu = (int)(LDS_LIMIT / BYTES);
-  per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // two 8-wave workgroups per CU, as field_fwd_kernel
-  int grid = 256 * per_cu;
-  if (grid > R) grid = R;
+  const int grid = field_render_grid<NS>(R);
   if (vd) {
-    auto k = field_render_kernel<T, NS, true>;
+    auto k = field_render_kernel<T, NS, true, 6>;
     SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
   } else {
-    auto k = field_render_kernel<T, NS, false>;
+    auto k = field_render_kernel<T, NS, false, 6>;
     SNERF_ALLOW_LDS(k, LDS_LIMIT);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FF_NW * 64), BYTES, st, a, R, o);
   }
@@ -270,9 +195,9 @@ extern "C" int snerf_kplanes_field_render(const snerf_kplanes_desc* desc, const 
                 (double)transmittance_cutoff);
   if (R == 0) return 0;
   SNERF_REQUIRE(planes && W_sigma && W_color && rgb_out && acc_out, "kplanes_field_render: null buffer");
-  SNERF_REQUIRE(coords->origins && coords->dirs && coords->times && coords->ebins, "kplanes_field_render: null ray buffer");
   FieldArgs a = {};
   a.d = *desc; a.planes = planes; a.c = *coords; a.N = (int64_t)R * coords->S; a.Wsig = W_sigma; a.Wcol = W_color;
   RayOut o = {transmittance_cutoff, rgb_out, acc_out, depth_median, depth_expected, median_index, samples_done};
+  if (desc->n_coords == 3) return launch_field_render_static(a, R, o, sigma->operands, (hipStream_t)stream, color->d_in != FF_GEO);
   FF_DISPATCH_FWD(launch_field_render, sigma->operands, desc->n_scales, a, R, o, (hipStream_t)stream, color->d_in != FF_GEO);
 }

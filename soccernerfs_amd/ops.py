@@ -51,7 +51,8 @@ def coords_from_rays(origins, dirs, times, ebins, aabb, rescale: bool) -> _lib.C
     c.mode = 1
     c.S = ebins.shape[-1] - 1
     c.rescale = int(rescale)
-    c.origins, c.dirs, c.times, c.ebins = origins.data_ptr(), dirs.data_ptr(), times.data_ptr(), ebins.data_ptr()
+    c.origins, c.dirs, c.ebins = origins.data_ptr(), dirs.data_ptr(), ebins.data_ptr()
+    c.times = times.data_ptr() if times is not None else None  # None: a static scene (3-coordinate descriptors never read it)
     a = aabb_host(aabb)
     for k in range(3):
         c.aabb_min[k] = a[0][k]
@@ -125,14 +126,14 @@ class SortedScatter:
     """Workspace + driver of the sorted plane-gradient scatter (csrc/kplanes_sorted.hip) for a fixed sample count N."""
 
     def __init__(self, ps: PlaneSet, N: int, device, gvec_dtype: torch.dtype = torch.float32, quotient: bool = False,
-                 fix_capacity: Optional[int] = None):
+                 fix_capacity: Optional[int] = None, desc: Optional[_lib.KPlanesDesc] = None):
         """gvec_dtype: element type of the per-plane gradient vectors between pass A and pass B -- float32 (exact) or bfloat16 (half the
         bytes of the step's largest intermediate; the scatter accumulates in fp32 either way).  quotient: the quotient form
         (scatter_quotient: one [N, C n_scales] tensor instead of the vectors; C = 32, concatenated scales) -- the vector buffer is then
-        not allocated."""
+        not allocated.  desc: the view of `ps` to sort and scatter for (default ps.desc(); ps.space_desc() = the space planes only)."""
         if gvec_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("gvec_dtype must be torch.float32 or torch.bfloat16")
-        self.ps, self.N, self.desc = ps, N, ps.desc()
+        self.ps, self.N, self.desc = ps, N, ps.desc() if desc is None else desc
         self.gvec_bf16 = int(gvec_dtype == torch.bfloat16)
         hc, ie = C.c_int64(0), C.c_int64(0)
         _lib.check(_lib.lib().snerf_kplanes_sort_workspace(C.byref(self.desc), C.c_int64(N), C.byref(hc), C.byref(ie)), "sort_workspace")
@@ -792,10 +793,13 @@ def adam_step(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps: float =
 
 
 def adam_planes_step(ps: PlaneSet, p_in, p_out, g, m, v, coefs, losses, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-12,
-                     grad_scale: float = 1.0, zero_grad: bool = True, shard_range=None, dyn: Optional[torch.Tensor] = None):
+                     grad_scale: float = 1.0, zero_grad: bool = True, shard_range=None, dyn: Optional[torch.Tensor] = None,
+                     desc: Optional[_lib.KPlanesDesc] = None):
     """Adam over one plane set with the plane regularisers fused in (ping-pong p_in -> p_out). coefs = (space_tv, time_smooth, sparse).
-    shard_range = (lo, hi): update only floats [lo, hi) of the segment (this rank's optimiser shard); all tensors are whole segments."""
-    desc = ps.desc()
+    shard_range = (lo, hi): update only floats [lo, hi) of the segment (this rank's optimiser shard); all tensors are whole segments.
+    desc: the view of `ps` to sweep (default ps.desc()); ps.space_desc() steps the space planes alone and leaves the planes between them, their
+    moments and their gradients untouched (the kernel locates its workgroups per plane, and the view's offsets are monotone)."""
+    desc = ps.desc() if desc is None else desc
     lo, hi = (0, ps.numel + 3 & ~3) if shard_range is None else shard_range
     _lib.check(_lib.lib().snerf_adam_planes_step_range(C.byref(desc), _ptr(p_in), _ptr(p_out), _ptr(g), _ptr(m), _ptr(v), coefs[0], coefs[1], coefs[2],
                                                        _ptr(losses) if losses is not None else None, REG_SLOTS if losses is not None else 0, lr,

@@ -186,11 +186,13 @@ class KPlanesRenderer:
     def render_frame(self, cameras: Cameras, index: int, anneal: Optional[float] = None, default_time: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """Camera `index` of `cameras` -> {"rgb": [H,W,3], "accumulation": [H,W,1], "depth": [H,W,1]} (device tensors, fresh per call): the keys and
         shapes of KPlanesModel.get_outputs_for_camera_ray_bundle; depth is the median depth, as the model renders it.
-        anneal: the proposal sampler's annealing exponent (default: default_anneal()); default_time: the time of a camera table without times."""
+        anneal: the proposal sampler's annealing exponent (default: default_anneal()); default_time: the time of a camera table without times
+        (not needed, and ignored, when the trainer is a static scene or has frozen time planes: its descriptors hold no time plane)."""
         tab = self._host_table(cameras)
         if not 0 <= index < len(tab["fx"]):
             raise IndexError(f"camera index {index} outside the table of {len(tab['fx'])}")
-        if tab["times"] is None and default_time is None:
+        static = getattr(self.trainer, "_static", False)  # three planes per scale (a static scene / frozen time planes): no kernel reads the time
+        if tab["times"] is None and default_time is None and not static:
             raise ValueError("the cameras carry no times (a camera path has them only if every entry has render_time) and K-Planes is a dynamic "
                              "model: pass default_time")
         H, W = cameras.height, cameras.width
@@ -209,7 +211,7 @@ class KPlanesRenderer:
         else:
             ra = _lib.RaygenFrameArgs()
         ra.fx, ra.fy, ra.cx, ra.cy = tab["fx"][index], tab["fy"][index], tab["cx"][index], tab["cy"][index]
-        ra.time = tab["times"][index] if tab["times"] is not None else float(default_time)
+        ra.time = tab["times"][index] if tab["times"] is not None else float(default_time if default_time is not None else 0.0)
         for k in range(12):
             ra.c2w[k] = tab["c2w"][index][k]
         ra.W, ra.H, ra.near_plane = W, H, self.cfg.near_plane
@@ -245,7 +247,7 @@ class KPlanesRenderer:
         if format not in ("png", "npy"):
             raise ValueError(f"format={format!r}: 'png' or 'npy' (video encoding is out of scope)")
         cameras = get_path_from_json(load_camera_path(path), camera_types=ALL_CAMERA_TYPES)
-        if cameras.times is None and default_time is None:
+        if cameras.times is None and default_time is None and not getattr(self.trainer, "_static", False):
             raise ValueError("the camera path has no render_time on every entry and no default_time was given: K-Planes needs a time per frame")
         os.makedirs(output_dir, exist_ok=True)
         files = []

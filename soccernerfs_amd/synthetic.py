@@ -80,12 +80,13 @@ def _cell_hash(ix: torch.Tensor, iy: torch.Tensor, salt: int) -> torch.Tensor:
     return ((h ^ (h >> 16)) & 0xFFFF).float() / 65536.0
 
 
-def shade(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, variant: str = "default") -> torch.Tensor:
+def shade(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, variant: str = "default", dynamic: bool = True) -> torch.Tensor:
     """Analytic colour in [0,1] for rays (o,d [N,3], unit d) at times [N].  variant "textured" (round 4; PSNR studies on content that does
     not saturate): the same pitch with fine grass / wear texture on it, an advertising board and a crowd stand behind the far touchline,
-    and ten players instead of three."""
+    and ten players instead of three.  dynamic=False leaves out players and ball: the empty scene the reference's dataparsers read from their
+    "empty" directory for static pre-training (broadcaststyle_dataparser.py `static`); the result does not depend on time."""
     if variant == "stadium":
-        return shade_stadium(o, d, time)
+        return shade_stadium(o, d, time, dynamic)
     textured = variant == "textured"
     assert variant in ("default", "textured")
     N = o.shape[0]
@@ -122,6 +123,8 @@ def shade(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, variant: str = "
                 c = base * (1 - bars[:, None]) + (1 - base) * bars[:, None]
             col = torch.where(hit[:, None], c, col)
             depth = torch.where(hit, tw, depth)
+    if not dynamic:
+        return col.clamp(0, 1)
     # dynamic content: three players (torso + head) that move a few body widths during the clip, and a ball on a parabolic arc
     tt = time
     z0 = torch.full_like(tt, -0.08)
@@ -204,7 +207,7 @@ def stadium_tracks(tt: torch.Tensor):
     return players, balls
 
 
-def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor) -> torch.Tensor:
+def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, dynamic: bool = True) -> torch.Tensor:
     dev = o.device
     sky = torch.stack([0.50 + 0.2 * d[:, 2], 0.66 + 0.15 * d[:, 2], 0.93 * torch.ones_like(d[:, 2])], -1).clamp(0, 1)
     inf = torch.full_like(d[:, 0], float("inf"))
@@ -241,6 +244,8 @@ def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor) -> torch
         seat = seat * (1.0 - 0.45 * ((ps[:, 2] - STADIUM_GROUND_Z) / 0.45).clamp(0, 1))[:, None]
         col = torch.where(hit[:, None], seat, col)
         depth = torch.where(hit, ts, depth)
+    if not dynamic:  # the empty stadium
+        return col.clamp(0, 1)
     players, balls = stadium_tracks(time)
     kits = ((0.85, 0.1, 0.1), (0.1, 0.15, 0.8), (0.95, 0.85, 0.1), (0.92, 0.92, 0.92), (0.08, 0.08, 0.08), (0.9, 0.4, 0.05), (0.5, 0.1, 0.6))
     head_up = torch.tensor([0.0, 0.0, 0.013], device=dev)
@@ -259,14 +264,15 @@ def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor) -> torch
     return col.clamp(0, 1)
 
 
-def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, device, chunk_rows: int = 135, variant: str = "default") -> Dict[str, torch.Tensor]:
+def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, device, chunk_rows: int = 135, variant: str = "default",
+                   dynamic: bool = True) -> Dict[str, torch.Tensor]:
     """uint8 images [M,H,W,3] on `device` for every (camera in cam_ids) x (time), plus per-image camera tables
     (one 'camera' per image, as nerfstudio's Cameras object holds them: c2w/intrinsics repeated per frame + times).
     cams may carry "distortion": OpenCV rows k1 k2 k3 k4 p1 p2, [n_cams,6] or [6] for all cameras.  The dataset is then shot through that lens
     (ops.generate_rays(distortion_params=...)) and the returned table carries "distortion" [M,6]; without the entry nothing changes.
     cams may carry "camera_type": an int or CameraType for all cameras, or one per camera [n_cams] (1 perspective, 2 fisheye, 3 equirectangular).
     The dataset is then shot with cameras of those types (ops.generate_rays(camera_type=...)) and the returned table carries "camera_type"
-    int32 [M]; without the entry nothing changes."""
+    int32 [M]; without the entry nothing changes.  dynamic=False: the empty scene (shade)."""
     from . import ops
 
     H, W = cams["height"], cams["width"]
@@ -306,7 +312,7 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             idx = torch.stack([torch.full_like(yy, m), yy, xx], -1).reshape(-1, 3)
             rays = ops.generate_rays(idx, table["fx"], table["fy"], table["cx"], table["cy"], table["c2w"], table["times"],
                                      distortion_params=table.get("distortion"), camera_type=table.get("camera_type"), validate_camera_type=False)
-            col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant)
+            col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant, dynamic)
             imgs[m, r0:r0 + rows.numel()] = (col.view(rows.numel(), W, 3) * 255.0 + 0.5).to(torch.uint8)
     return {"images": imgs, **table, "width": W, "height": H}
 

@@ -158,6 +158,15 @@ class KPlanesTrainConfig:
     # (snerf_kplanes_gather_bwd_coords; bin edges are constants).  It needs the fp32 feature gradient, so the step takes the flow without the
     # quotient epilogue.  Off: no buffer, no launch, the step as it was.
     ray_gradients: bool = False
+    # KPlanesModelConfig.freeze_time_planes (NS/models/kplanes.py:174-177, NS/fields/kplanes_field.py:95-99): the static pre-training stage of the
+    # reference's two-stage recipe.  The planes that hold the time axis are allocated, initialised to ones and saved, but never gathered, never
+    # given a gradient and never stepped (values and Adam moments stay bitwise what they were); the four time terms leave the loss dict
+    # (kplanes.py:438).  Every kernel then runs on PlaneSet.space_desc(), the three-plane view of the same buffers.
+    # A spacetime_resolution / proposal_resolutions of length 3 is the original static K-Planes model (kplanes_field.py:59-61) on the same code.
+    freeze_time_planes: bool = False
+    # KPlanesModelConfig.freeze_space_planes: NOT built on this trainer (it raises): in the reference only YT and ZT receive a data gradient under
+    # it while the TV term still moves the space planes (kplanes_field.py:101-116); ops.interpolate_kplanes and the autograd KPlanesModel have it.
+    freeze_space_planes: bool = False
 
 
 class KPlanesTrainer(FusedStep):
@@ -168,6 +177,27 @@ class KPlanesTrainer(FusedStep):
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+        # static scenes: decided by name before anything is allocated
+        nc = len(cfg.spacetime_resolution)
+        if nc not in (3, 4) or any(len(r) != nc for r in cfg.proposal_resolutions):
+            raise ValueError(f"spacetime_resolution and every entry of proposal_resolutions must all have 3 (static scene) or all have 4 values; got "
+                             f"{list(cfg.spacetime_resolution)} and {[list(r) for r in cfg.proposal_resolutions]}")
+        if cfg.freeze_time_planes and nc == 3:
+            raise ValueError("freeze_time_planes on a 3-coordinate model (len(spacetime_resolution) == 3): it has no time planes to freeze")
+        if cfg.freeze_space_planes:
+            raise NotImplementedError("freeze_space_planes is not built on the fused trainer (the reference gives only the YT and ZT planes a data gradient "
+                                      "under it while the TV term still moves the space planes); the autograd KPlanesModel has it")
+        # True: every kernel sees three planes per scale -- a 3-coordinate model, or the space planes of frozen time planes (PlaneSet.space_desc())
+        self._static = bool(cfg.freeze_time_planes or nc == 3)
+        self._frozen = bool(cfg.freeze_time_planes)
+        if self._static:
+            what = "freeze_time_planes" if cfg.freeze_time_planes else "a 3-coordinate spacetime_resolution"
+            if self.world > 1:
+                raise NotImplementedError(f"{what} with world > 1 (multi-GPU) is not built: the sharded exchange is laid out for six planes per scale")
+            if cfg.ray_gradients:
+                raise NotImplementedError(f"{what} with ray_gradients is not built: the camera optimiser is pinned on the six-plane model only")
+            if cfg.pipeline_sweep:
+                raise NotImplementedError(f"{what} with pipeline_sweep is not built: the split of the optimiser sweep is by whole six-plane scales")
         # world > 1: reduce-scatter + sharded Adam + all-gather for the field planes instead of one all-reduce (see dist.py)
         if cfg.ray_gradients:
             # what the ray gradient does not cover raises here, by name and before anything is allocated, instead of training the poses on a
@@ -254,6 +284,7 @@ class KPlanesTrainer(FusedStep):
         # the regulariser-fused optimiser sweep reads neighbours of the OLD parameters: parameters ping-pong between two buffers
         self.fuse_reg_into_adam = cfg.fuse_reg_into_adam
         self._params_alt = torch.zeros_like(self.params)
+        self._sync_frozen_halves()
         self._exchange = []  # per exchange chunk: dict(lo, hi, g_shard, p_shard, ...) -- see _plan_exchange
         # ---- work buffers ----
         R = num_rays
@@ -278,6 +309,10 @@ class KPlanesTrainer(FusedStep):
         }
         # sorted plane-gradient scatter for the main field (csrc/kplanes_sorted.hip): ~6x fewer atomic requests
         self.sorted_scatter = cfg.sorted_scatter
+        # what every launch sees of the plane sets: all six planes per scale, or the three space planes (self._static)
+        view = (lambda ps: ps.space_desc()) if self._static else (lambda ps: ps.desc())
+        self._desc_field = view(self.field_planes)
+        self._desc_prop = [view(p) for p in self.prop_planes]
         self._gvec_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[cfg.gvec_dtype]
         self.quotient_scatter = bool(cfg.quotient_scatter and self.sorted_scatter and not cfg.deterministic
                                      and cfg.gvec_dtype == "fp32" and self.lib_quotient_ok(R * S2))
@@ -290,9 +325,8 @@ class KPlanesTrainer(FusedStep):
                 if net.desc.operands != 0:
                     self._mlp_ws[gname] = torch.zeros(int(_lib.lib().snerf_mlp_gw_workspace_floats(C.byref(net.desc))), dtype=torch.float32, device=self.dev)
         self._ss = ops.SortedScatter(self.field_planes, R * S2, self.dev, self._gvec_dtype, quotient=self.quotient_scatter,
-                                     fix_capacity=cfg.fix_capacity)
+                                     fix_capacity=cfg.fix_capacity, desc=self._desc_field)
         self._fix_peak_host = torch.zeros(1, dtype=torch.int32).pin_memory() if self.quotient_scatter else None
-        self._ss.desc = self.field_planes.desc()
         if cfg.emulate_transports not in ("", "grad", "param", "both"):
             raise ValueError(f"emulate_transports must be '', 'grad', 'param' or 'both', got {cfg.emulate_transports!r}")
         self._sort_done = None
@@ -305,8 +339,6 @@ class KPlanesTrainer(FusedStep):
         self._steps_since_update = 0  # ProposalNetworkSampler bookkeeping (ray_samplers.py:546-557)
         self.last = {}
         self.lib = _lib.lib()
-        self._desc_field = self.field_planes.desc()
-        self._desc_prop = [p.desc() for p in self.prop_planes]
         self.fused_field = bool(cfg.fused_field and self.lib.snerf_kplanes_field_fwd_supported(
             C.byref(self._desc_field), C.byref(self.sigma_net.desc), C.byref(self.color_net.desc)))
         # view-dependent colour net: with 16-bit operands its backward forms [SH | h] on chip (snerf_kplanes_color_bwd_vd); the generic MLP kernels
@@ -319,7 +351,8 @@ class KPlanesTrainer(FusedStep):
             dt16 = torch.bfloat16 if self.sigma_net.desc.operands == 1 else torch.float16
             self.buf["feat16"] = torch.empty(R * self.S[2], self.field_planes.out_dim, dtype=dt16, device=self.dev)
         # plain attribute, so that A-B tools can flip it between steps; the order buffer exists either way (train_step allocates nothing)
-        self.field_fwd_time_order = bool(cfg.field_fwd_time_order and self.fused_field and self.S[2] % 32 == 0 and R <= 16384)
+        # (never on the three-plane view: the walk exists for the time planes' rows)
+        self.field_fwd_time_order = bool(cfg.field_fwd_time_order and self.fused_field and self.S[2] % 32 == 0 and R <= 16384 and not self._static)
         self._ray_order = torch.zeros(R, dtype=torch.int32, device=self.dev)
         self.quotient_epilogue = bool(cfg.quotient_epilogue and self.quotient_scatter and self.fused_field and self.sigma_net.desc.operands == 1
                                       and self.sigma_net.desc.hidden == 128 and self.sigma_net.desc.n_hidden == 1)
@@ -339,6 +372,29 @@ class KPlanesTrainer(FusedStep):
                                                     for dp, net in zip(self._desc_prop, self.prop_nets)))
         if self.world > 1:
             self._plan_exchange()
+
+    @torch.no_grad()
+    def _sync_frozen_halves(self):
+        """freeze_time_planes: the optimiser sweeps ping-pong between self.params and self._params_alt but write the space planes only, so both halves
+        must hold the frozen planes: called wherever parameters arrive from outside a step (construction, restart, checkpoint / oracle import)."""
+        if self._frozen:
+            self._params_alt.copy_(self.params)
+
+    def _plain_adam_ranges(self):
+        """(lo, hi, parameter group) float ranges of the flat buffer that the plain (regulariser-free) Adam sweep steps: the two groups whole, or,
+        with frozen time planes, everything but those planes -- XY | XZ and YZ of every scale are the contiguous runs between them."""
+        if not self._frozen:
+            return [(0, self.n_proposal_params, "proposal_networks"), (self.n_proposal_params, self.n_params, "fields")]
+        out = []
+        sets = [(f"prop{i}.planes", ps, "proposal_networks") for i, ps in enumerate(self.prop_planes)] + [("field.planes", self.field_planes, "fields")]
+        for name, ps, g in sets:
+            o = self.off[name][0]
+            for offs in ps.offsets:
+                out += [(o + offs[0], o + offs[2], g), (o + offs[3], o + offs[4], g)]
+        for name, g in [(f"prop{i}.mlp", "proposal_networks") for i in range(len(self.prop_nets))] + [("field.sigma", "fields"), ("field.color", "fields")]:
+            o, n = self.off[name]
+            out.append((o, o + _align4(n), g))
+        return out
 
     def _plan_exchange(self):
         """Sharded optimiser (world > 1): the field-plane segment is exchanged in CHUNKS so that the reduce-scatter of a chunk starts as soon
@@ -460,6 +516,9 @@ class KPlanesTrainer(FusedStep):
         # the kernels read these buffers through raw pointers: insist on contiguous fp32 device tensors of the expected shapes
         rays = dict(rays)
         for k, cols in (("origins", 3), ("directions", 3), ("times", 1)):
+            if k == "times" and self._static and rays.get(k) is None:
+                rays[k] = None  # no kernel of the three-plane view reads the rays' times
+                continue
             rays[k] = ops._f32c(rays[k], f"rays[{k!r}]")
             if rays[k].numel() != R * cols:
                 raise RuntimeError(f"rays[{k!r}] must hold {R} x {cols} values, got {tuple(rays[k].shape)}")
@@ -469,7 +528,7 @@ class KPlanesTrainer(FusedStep):
             rng["u"] = [ops._f32c(u, "rng['u']") for u in rng["u"]]
             if rng["bg"].numel() != 3 * R or any(u.shape[0] != R for u in rng["u"]) or rng["t_rand"].shape[0] != R:
                 raise RuntimeError("rng draws must have one row per ray")
-        o, d, t = rays["origins"], rays["directions"], rays["times"].reshape(-1)
+        o, d, t = rays["origins"], rays["directions"], rays["times"].reshape(-1) if rays["times"] is not None else None
         if self.field_fwd_time_order:  # first on the main stream: done long before the field forward, under the previous step's sweep
             with self._span("ray_time_order"):
                 _lib.check(self.lib.snerf_ray_time_order(self._p(t), R, self._p(self._ray_order), self._st), "ray_time_order")
@@ -580,8 +639,7 @@ class KPlanesTrainer(FusedStep):
                                                     self._p(b["reg"][1 + lvl]), ops.REG_SLOTS, 1, self._st), "plane_reg")
 
     def lib_quotient_ok(self, N: int) -> bool:
-        d = self.field_planes.desc()
-        return bool(_lib.lib().snerf_kplanes_quotient_supported(C.byref(d), C.c_int64(N)))
+        return bool(_lib.lib().snerf_kplanes_quotient_supported(C.byref(self._desc_field), C.c_int64(N)))
 
     def _scatter_field_scales(self, co, lo: int, hi: int, fixup: bool = True):
         """Pass B of the field's sorted scatter for scales [lo, hi): product form (gradient vectors from gradvec / the fused backward) or
@@ -619,7 +677,8 @@ class KPlanesTrainer(FusedStep):
             self._mlp_bwd(self.sigma_net, "field.sigma", sl(b["feat16"] if self._fwd_fused else b["feat"]), F, N, sl(b["gh"]), 16, 15, b["gdens"][2][r0:r1],
                           sl(b["gfeat"]), F, x16=self._fwd_fused)
         rays = self.rays
-        co = ops.coords_from_rays(rays["origins"][r0:r1], rays["directions"][r0:r1], rays["times"].reshape(-1)[r0:r1], b["eb"][2][r0:r1], self.aabb, True)
+        times = rays["times"].reshape(-1)[r0:r1] if rays["times"] is not None else None
+        co = ops.coords_from_rays(rays["origins"][r0:r1], rays["directions"][r0:r1], times, b["eb"][2][r0:r1], self.aabb, True)
         if self.sorted_scatter and self.grads_fx is None and self._sort_done is not None and r0 == 0 and r1 == self.R:
             torch.cuda.current_stream().wait_event(self._sort_done)
             ss = self._ss
@@ -879,6 +938,9 @@ class KPlanesTrainer(FusedStep):
         pr = reg[1] + reg[2]
         d["space_tv_proposal_loss"], d["time_smoothness_proposal_loss"], d["sparse_transients_proposal_loss"] = (
             pr[0] * co["space_tv_proposal_loss"], pr[1] * co["time_smoothness_proposal_loss"], pr[2] * co["sparse_transients_proposal_loss"])
+        if self._static:  # kplanes.py:438: no time terms for a static model or frozen time planes
+            for k in ("time_smoothness_loss", "sparse_transients_loss", "time_smoothness_proposal_loss", "sparse_transients_proposal_loss"):
+                del d[k]
         return d
 
     # ---- world > 1: reduce-scatter -> sharded Adam -> all-gather for the field planes (dist.py) ----
@@ -919,6 +981,7 @@ class KPlanesTrainer(FusedStep):
         self.synchronize(check_overflow=False)  # a new run starts here: an overflow recorded by the old one is cleared below, not raised
         if params is not None:
             self.params.copy_(params)
+        self._sync_frozen_halves()
         for t in (self.exp_avg, self.exp_avg_sq, self.grads) + ((self.grads_fx,) if self.grads_fx is not None else ()):
             t.zero_()
         for d in self._dyn.values():
@@ -1096,7 +1159,7 @@ class KPlanesTrainer(FusedStep):
                 self.vviews["field.planes"], tuple(co[k] for k in ("space_tv_loss", "time_smoothness_loss", "sparse_transients_loss")),
                 self.buf["reg"][0], self.step + 1, lr)
         self._prepare_group("fields", lr)
-        kw = dict(eps=cfg.adam_eps, grad_scale=self._grad_scale, zero_grad=True, shard_range=rng_, dyn=self._dyn["fields"])
+        kw = dict(eps=cfg.adam_eps, grad_scale=self._grad_scale, zero_grad=True, shard_range=rng_, dyn=self._dyn["fields"], desc=self._desc_field)
         if not side:
             with self._span(span):
                 ops.adam_planes_step(*args, **kw)
@@ -1136,7 +1199,7 @@ class KPlanesTrainer(FusedStep):
             self._prepare_group("fields", lr)
             self._prepare_group("proposal_networks", lr)
             with self._span("adam_step"):  # one sweep per parameter group (= per torch optimiser of the reference)
-                for lo, hi, g in ((0, self.n_proposal_params, "proposal_networks"), (self.n_proposal_params, self.n_params, "fields")):
+                for lo, hi, g in self._plain_adam_ranges():
                     ops.adam_step(self.params[lo:hi], self.grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.step + 1, lr, eps=cfg.adam_eps,
                                   grad_scale=gs, zero_grad=True, dyn=self._dyn[g])
             self._finish_step()
@@ -1189,7 +1252,7 @@ class KPlanesTrainer(FusedStep):
             with self._span("adam_planes." + name.split(".")[0]):
                 ops.adam_planes_step(ps, sl(self.params, name), sl(new, name), self.gviews[name], self.mviews[name], self.vviews[name],
                                      tuple(co[k] for k in keys), self.buf["reg"][row], self.step + 1, lr, eps=cfg.adam_eps, grad_scale=gs,
-                                     dyn=self._dyn["proposal_networks"])
+                                     dyn=self._dyn["proposal_networks"], desc=self._desc_prop[row - 1])
         self._adam_mlps(new, off, lr, gs)
         self._params_alt = self.params
         self._repoint(new)
@@ -1298,15 +1361,22 @@ class KPlanesTrainer(FusedStep):
             opt.update(cam_opt)
         return CK.save_checkpoint(checkpoint_dir, max(self.step - 1, 0), root, opt, save_only_latest_checkpoint, extra_pipeline=extra)
 
-    def load_checkpoint(self, load_dir: str, load_step: Optional[int] = None, camera_optimizer=None) -> int:
+    def load_checkpoint(self, load_dir: str, load_step: Optional[int] = None, camera_optimizer=None, params_only: bool = False) -> int:
         """Parameters (+ Adam moments when the file holds them) from a nerfstudio checkpoint; returns the step training resumes at.
-        camera_optimizer: takes its state from the file too (zeros when the file has none)."""
+        camera_optimizer: takes its state from the file too (zeros when the file has none).
+        params_only: the hand-over between the two stages of the reference's recipe (static pre-training, then the dynamics): the parameters are
+        loaded, the moments are zero and the step is 0 -- the new stage runs its own schedule from the pre-trained planes; returns 0.  A checkpoint
+        written with freeze_time_planes loads into a trainer without it and the other way round (same keys, same shapes)."""
         from . import checkpoint as CK
 
         self.synchronize()
         root = self._named_module()
         start, moments = CK.load_checkpoint(load_dir, root, load_step, camera_optimizer=camera_optimizer)
         names = self._ck_names()
+        if params_only:
+            self.restart()  # moments, counters and the step cleared; the parameters just loaded stay (both ping-pong halves: below)
+            self._params_alt.copy_(self.params)
+            return 0
         for ck, (m, v, _) in moments.items():
             self.mviews[names[ck]].copy_(m.reshape(-1).to(self.dev))
             self.vviews[names[ck]].copy_(v.reshape(-1).to(self.dev))
@@ -1325,3 +1395,4 @@ class KPlanesTrainer(FusedStep):
         for i in range(len(self.prop_planes)):
             self.prop_planes[i].load_reference([[t.to(self.dev) for t in P["prop_grids"][i]]])
             self.prop_nets[i].load_linear_weights([w.to(self.dev) for w in P["prop_sigma"][i]])
+        self._sync_frozen_halves()

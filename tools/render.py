@@ -51,9 +51,11 @@ def main(argv=None):
     ap.add_argument("--fused-tail", action="store_true", help="field forward + weights + compositing as ONE kernel (same bits; measured slower, DESIGN 4.9)")
     ap.add_argument("--default-time", type=float, default=None, help="time of every frame when the path carries no render_time")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="KPlanesTrainConfig override, repeatable")
+    ap.add_argument("--freeze-time-planes", action="store_true", help="the checkpoint is a static pre-training stage (KPlanesTrainConfig.freeze_time_planes): "
+                    "render from the space planes alone; the path needs no render_time and --default-time is ignored")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
-    cfg = config_from_overrides(args.set)
+    cfg = config_from_overrides(args.set + (["freeze_time_planes=True"] if args.freeze_time_planes else []))
     trainer = KPlanesTrainer(cfg, 4096, args.device)
     step = trainer.load_checkpoint(args.load_dir, args.load_step)
     renderer = KPlanesRenderer(trainer, rays_per_chunk=args.eval_num_rays_per_chunk, transmittance_cutoff=args.transmittance_cutoff,

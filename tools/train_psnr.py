@@ -100,6 +100,29 @@ def stats(xs):
     return {"mean": mean, "min": min(xs), "max": max(xs), "std": (sum((x - mean) ** 2 for x in xs) / max(n - 1, 1)) ** 0.5, "n": n}
 
 
+def static_pretrain(args, cfg, trainer, train, R, dev):
+    """Stage 1 of the reference's two-stage recipe (broadcaststyle_dataparser.py `static`): args.static_pretrain steps of a trainer with
+    freeze_time_planes on the EMPTY scene seen by the training cameras (uniform pixels; one frame per camera, the scene does not move), then the
+    hand-over: `trainer` starts its own schedule from the pre-trained planes (load_checkpoint(params_only=True))."""
+    import dataclasses
+    import tempfile
+
+    empty = train["empty"]
+    M, H, W = empty["images"].shape[:3]
+    stage1 = KPlanesTrainer(dataclasses.replace(cfg, freeze_time_planes=True, ray_gradients=False), R, dev)
+    t0 = time.time()
+    for _ in range(args.static_pretrain):
+        idx, target = ops.sample_pixels_uniform(torch.rand(R, 3, device=dev), M, H, W, images=empty["images"])
+        rays = ops.generate_rays(idx, empty["fx"], empty["fy"], empty["cx"], empty["cy"], empty["c2w"], empty["times"], aabb=stage1.aabb,
+                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"))
+        stage1.train_step(rays, target)
+    with tempfile.TemporaryDirectory() as d:
+        stage1.save_checkpoint(d)
+        trainer.load_checkpoint(d, params_only=True)
+    print(f"[seed {cfg.seed}] static pre-training: {args.static_pretrain} steps with frozen time planes on the empty scene in {time.time() - t0:.0f} s, "
+          f"rgb_loss {float(stage1.loss_dict()['rgb_loss']):.5f}", flush=True)
+
+
 def run_one(args, seed, train, sets, ist, dev, log_steps=True):
     torch.manual_seed(seed)
     random.seed(seed)
@@ -109,6 +132,9 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
                              emulate_transports=args.emulate_transports, quotient_epilogue=not args.no_quotient_epilogue, fused_proposal=not args.no_fused_proposal,
                              sigma_operands=args.sigma_operands, color_operands=args.color_operands, proposal_operands=args.proposal_operands,
                              ray_gradients=args.optimize_cameras)
+    if args.static_scene:  # the original static K-Planes model: three planes per scale, no time axis (kplanes_field.py:59-61)
+        cfg.spacetime_resolution = tuple(cfg.spacetime_resolution)[:3]
+        cfg.proposal_resolutions = tuple(tuple(r)[:3] for r in cfg.proposal_resolutions)
     R = 4096
     if args.standin:
         # the reference's algorithm in stock PyTorch (oracle/torch_standin.py: checker / baseline code, imported ONLY for this mode) on the same
@@ -123,9 +149,12 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
             trainer.load_oracle_params(KO.make_kplanes_params(seed=seed, **TS.PRESET))
         if args.no_overlap:
             trainer.overlap, trainer.async_field_adam = False, False
+        if args.static_pretrain:
+            static_pretrain(args, cfg, trainer, train, R, dev)
     M, H, W = train["images"].shape[:3]
     batch = {"image": train["images"], "image_idx": torch.arange(M, device=dev), "ist_weights": ist, "iter_steps": 0}
-    sampler = DynamicBasedPixelSampler(R, is_pixel_ratio=0.15, iters_to_start_ist=2000, mask_ist_weights=args.mask_ist)
+    # (an empty scene has no temporal differences to draw importance rays from: uniform pixels throughout)
+    sampler = DynamicBasedPixelSampler(R, is_pixel_ratio=0.15, iters_to_start_ist=2000 if not args.static_scene else args.steps + 1, mask_ist_weights=args.mask_ist)
     mask = train.get("mask") if args.use_masks else None  # --use-masks: every uniform draw inside the mask (and with --mask-ist the IST draws too)
     if mask is not None:
         batch["mask"] = mask
@@ -256,6 +285,9 @@ def main():
     ap.add_argument("--oracle-init", action="store_true", help="HIP trainer from the stand-in's initial parameters of the same seed")
     ap.add_argument("--scene", default="default", choices=["default", "textured"], help="synthetic.shade variant (textured: grass grain, board, crowd, ten players)")
     ap.add_argument("--no-overlap", action="store_true", help="single-stream step (A/B against stream-ordering effects)")
+    ap.add_argument("--static-pretrain", type=int, default=0, metavar="N", help="N steps with freeze_time_planes on the empty scene (no players, no ball) first, "
+                    "then the usual run from those planes (KPlanesTrainer.load_checkpoint(params_only=True)); compare against --steps raised by N")
+    ap.add_argument("--static-scene", action="store_true", help="a 3-coordinate model (three planes per scale, no time axis) on the empty scene")
     # a value such as -0.25,0.08,... starts with '-' and is no plain number, so argparse would read it as an option: hand it over as --lens=VALUE
     argv = sys.argv[1:]
     for i in range(len(argv) - 1):
@@ -286,6 +318,10 @@ def main():
         ap.error("--use-masks needs --overlay")
     if args.mask_ist and not args.use_masks:
         ap.error("--mask-ist needs --use-masks")
+    if (args.static_pretrain or args.static_scene) and (args.standin or args.optimize_cameras):
+        ap.error("--static-pretrain / --static-scene run on the HIP trainer without the camera optimiser")
+    if args.static_pretrain and args.static_scene:
+        ap.error("--static-pretrain prepares a dynamic model; a --static-scene model has no second stage")
     dev = torch.device("cuda:0")
     cams = synthetic.make_cameras(20, 960, 540)
     novel_cams = synthetic.make_novel_cameras(3, 960, 540)
@@ -297,9 +333,12 @@ def main():
     elif args.ignore_lens:
         ap.error("--ignore-lens needs --lens")
     times = synthetic.frame_times(100, 3)
-    train = synthetic.render_dataset(cams, times, list(range(19)), dev, chunk_rows=540, variant=args.scene)
-    held = synthetic.render_dataset(cams, times, [19], dev, chunk_rows=540, variant=args.scene)
-    novel = synthetic.render_dataset(novel_cams, times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene)
+    dyn = not args.static_scene
+    train = synthetic.render_dataset(cams, times, list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
+    held = synthetic.render_dataset(cams, times, [19], dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
+    novel = synthetic.render_dataset(novel_cams, times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
+    if args.static_pretrain:  # the reference's "empty" directory: the training cameras' view of the scene without players and ball
+        train["empty"] = synthetic.render_dataset(cams, times[:1], list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=False)
     if args.overlay:
         box = [int(v) for v in args.overlay.split(",")]
         if len(box) != 4:
@@ -333,6 +372,7 @@ def main():
            "quotient_epilogue": not args.no_quotient_epilogue, "fused_proposal": not args.no_fused_proposal,
            "pose_noise": args.pose_noise or None, "pose_noise_seed": args.pose_noise_seed if args.pose_noise else None,
            "optimize_cameras": args.optimize_cameras, "share_poses_per_camera": args.share_poses_per_camera,
+           "static_pretrain_steps": args.static_pretrain, "static_scene": args.static_scene,
            "eval_sets": {"camera_20": "20th arc camera (reference 'all' split eval camera; extrapolated view), %d frames" % len(sets["camera_20"][1]),
                          "novel": "3 evaluation-only cameras between training cameras (interpolated views), %d images" % len(sets["novel"][1]),
                          "train": "4 training images"},

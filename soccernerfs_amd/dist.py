@@ -134,20 +134,19 @@ class CAbiComm:
         self._lib, self._C = _lib, C
         ident = (C.c_ubyte * 128)()
         if self.rank == 0:
-            _lib.check(_lib.lib().snerf_comm_unique_id(ident), "comm_unique_id")
+            _lib.call("comm_unique_id", ident)
         t = torch.tensor(list(ident), dtype=torch.uint8, device=device if _is_nccl(group) else "cpu")
         dist.broadcast(t, src=dist.get_global_rank(group, 0) if hasattr(dist, "get_global_rank") else 0, group=group)
         ident = (C.c_ubyte * 128)(*t.cpu().tolist())
         self._comm = C.c_void_p()
-        _lib.check(_lib.lib().snerf_comm_create(self.world, self.rank, ident, C.byref(self._comm)), "comm_create")
+        _lib.call("comm_create", self.world, self.rank, ident, C.byref(self._comm))
 
     def all_reduce_sum_(self, flat: torch.Tensor) -> float:
         C = self._C
-        self._lib.check(self._lib.lib().snerf_allreduce_grads(self._comm, C.c_void_p(flat.data_ptr()), C.c_int64(flat.numel()),
-                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "allreduce_grads")
+        self._lib.call("allreduce_grads", self._comm, flat.data_ptr(), flat.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         return 1.0 / self.world
 
     def close(self):
         if self._comm:
-            self._lib.check(self._lib.lib().snerf_comm_destroy(self._comm), "comm_destroy")
+            self._lib.call("comm_destroy", self._comm)
             self._comm = None

@@ -130,6 +130,10 @@ class FusedStep(FlatParams):
     _timing, _timing_all = None, False
     _ck = staticmethod(_lib.check)  # every launch's return code goes through here (NerfplayerStep counts them)
 
+    def _call(self, name: str, *args):
+        """Launches snerf_<name>(*args); the code goes through _ck under the entry's own name."""
+        self._ck(_lib.entries[name](*args), name)  # filled when the subclass loaded self.lib
+
     def _p(self, t, off_floats: int = 0):
         return C.c_void_p(t.data_ptr() + 4 * off_floats)
 
@@ -154,24 +158,24 @@ class FusedStep(FlatParams):
     # ---- launches ----
     def _mlp_fwd(self, net, X, ldx, N, Y, ldy, aux_col=-1, aux=None):
         with self._span(f"mlp_fwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
-            self._ck(self.lib.snerf_mlp_fwd(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N), self._p(Y), ldy, aux_col,
-                                            self._p(aux) if aux is not None else None, self._st), "mlp_fwd")
+            self._call("mlp_fwd", C.byref(net.desc), self._p(net.params), self._p(X), ldx, N, self._p(Y), ldy, aux_col,
+                       self._p(aux) if aux is not None else None, self._st)
 
     def _mlp_bwd(self, net, gW, X, ldx, N, gY, ldgy, aux_col, gaux, gX, ldgx):
         """gW: the net's view of self.grads; in deterministic mode the weight gradient goes to the fixed-point cells behind it."""
         with self._span(f"mlp_bwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
             fx = self.grads_fx is not None
-            self._ck((self.lib.snerf_mlp_bwd_fx if fx else self.lib.snerf_mlp_bwd)(
-                C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N), self._p(gY) if gY is not None else None, ldgy, aux_col,
-                self._p(gaux) if gaux is not None else None, self._p(gX) if gX is not None else None, ldgx, self._p(self.fx(gW) if fx else gW),
-                self._st), "mlp_bwd_fx" if fx else "mlp_bwd")
+            self._call("mlp_bwd_fx" if fx else "mlp_bwd",
+                       C.byref(net.desc), self._p(net.params), self._p(X), ldx, N, self._p(gY) if gY is not None else None, ldgy, aux_col,
+                       self._p(gaux) if gaux is not None else None, self._p(gX) if gX is not None else None, ldgx, self._p(self.fx(gW) if fx else gW),
+                       self._st)
 
     def _spaced_bins(self, t_rand):
         """The first level's bins from nears / fars; t_rand = None: no jitter."""
         b, rays = self.buf, self.rays
-        self._ck(self.lib.snerf_spaced_bins(self._p(rays["nears"]), self._p(rays["fars"]), self._p(t_rand) if t_rand is not None else None,
-                                            t_rand.shape[-1] if t_rand is not None else 0, self._fwd_rays, self.S[0], self.SPACING, self._p(b["sb"][0]),
-                                            self._p(b["eb"][0]), self._st), "spaced_bins")
+        self._call("spaced_bins", self._p(rays["nears"]), self._p(rays["fars"]), self._p(t_rand) if t_rand is not None else None,
+                   t_rand.shape[-1] if t_rand is not None else 0, self._fwd_rays, self.S[0], self.SPACING, self._p(b["sb"][0]),
+                   self._p(b["eb"][0]), self._st)
 
     def _resample(self, lvl, rand, anneal):
         """density[lvl] -> weights[lvl] (stored) -> PDF sample level lvl+1 bins."""
@@ -186,7 +190,7 @@ class FusedStep(FlatParams):
         a.R, a.S_prev, a.S, a.kind = self._fwd_rays, self.S[lvl], self.S[lvl + 1], self.SPACING
         a.anneal, a.histogram_padding, a.eps = anneal, 0.01, 1e-5
         with self._span("pdf_resample"):
-            self._ck(self.lib.snerf_pdf_resample(C.byref(a), self._st), "pdf_resample")
+            self._call("pdf_resample", C.byref(a), self._st)
 
     def _render_fwd(self, training: bool, bg_mode: int, bg: Optional[torch.Tensor], depth: str):
         """Compositing of the nerf level: rgb_out / acc / depth (`depth` = the RenderArgs field the model renders: "depth_median" or
@@ -199,7 +203,7 @@ class FusedStep(FlatParams):
         a.R, a.S, a.training = self._fwd_rays, self.S[2], int(training)
         a.rgb_out, a.acc_out = b["rgb_out"].data_ptr(), b["acc"].data_ptr()
         setattr(a, depth, b["depth"].data_ptr())
-        self._ck(self.lib.snerf_render_fwd(C.byref(a), self._st), "render_fwd")
+        self._call("render_fwd", C.byref(a), self._st)
 
     def _ray_train(self, target, bg, go_scale: float, dist_scale: float, median_depth: bool, dyn: Optional[torch.Tensor]):
         """The nerf level's weights -> compositing -> MSE / distortion backward -> weights backward as ONE launch (snerf_ray_train_fwd_bwd,
@@ -213,25 +217,25 @@ class FusedStep(FlatParams):
         ra.sqerr_rays, ra.dist_rays, ra.g_rgb, ra.g_density = b["sqerr"].data_ptr(), b["dist_rays"].data_ptr(), b["grgb"].data_ptr(), b["gdens"][2].data_ptr()
         ra.g_weights, ra.nonfinite_flag = None, dyn.data_ptr() if dyn is not None else None
         with self._span("ray_train_fwd_bwd"):
-            self._ck(self.lib.snerf_ray_train_fwd_bwd(C.byref(ra), self._st), "ray_train_fwd_bwd")
+            self._call("ray_train_fwd_bwd", C.byref(ra), self._st)
 
     def _mse_distortion_bwd(self, target, bg, go_scale: float, dist_scale: float):
         """The unfused form, first two of three: MSELoss folded into the render backward (g_rgb_out = go_scale * (rgb_out - target); value lazily
         from sqerr) writes gw[2] and grgb, the distortion loss adds to gw[2].  The caller adds its own terms to gw[2], then _weights_bwd(2)."""
         b, R, S2 = self.buf, self.R, self.S[2]
-        self._ck(self.lib.snerf_render_mse_bwd(self._p(b["w"][2]), self._p(b["rgb"]), self._p(bg), 0, self._p(b["rgb_out"]), self._p(target), go_scale, R, S2,
-                                               self._p(b["gw"][2]), self._p(b["grgb"]), self._p(b["sqerr"]), self._st), "render_mse_bwd")
-        self._ck(self.lib.snerf_distortion(self._p(b["w"][2]), self._p(b["sb"][2]), R, S2, dist_scale, self._p(b["dist_rays"]), self._p(b["gw"][2]), 1,
-                                           self._st), "distortion")
+        self._call("render_mse_bwd", self._p(b["w"][2]), self._p(b["rgb"]), self._p(bg), 0, self._p(b["rgb_out"]), self._p(target), go_scale, R, S2,
+                   self._p(b["gw"][2]), self._p(b["grgb"]), self._p(b["sqerr"]), self._st)
+        self._call("distortion", self._p(b["w"][2]), self._p(b["sb"][2]), R, S2, dist_scale, self._p(b["dist_rays"]), self._p(b["gw"][2]), 1,
+                   self._st)
 
     def _weights_bwd(self, lvl: int, dyn: Optional[torch.Tensor] = None):
         """gw[lvl] -> gdens[lvl]; dyn as in _ray_train."""
         b = self.buf
-        self._ck(self.lib.snerf_weights_bwd(self._p(b["dens"][lvl]), self._p(b["eb"][lvl]), self._p(b["gw"][lvl]), self.R, self.S[lvl], self._p(b["gdens"][lvl]),
-                                            0, self._p(dyn) if dyn is not None else None, self._st), "weights_bwd")
+        self._call("weights_bwd", self._p(b["dens"][lvl]), self._p(b["eb"][lvl]), self._p(b["gw"][lvl]), self.R, self.S[lvl], self._p(b["gdens"][lvl]),
+                   0, self._p(dyn) if dyn is not None else None, self._st)
 
     def _interlevel(self, lvl: int, mult: float, with_grad: bool):
         """Proposal supervision of level lvl (interlevel loss, losses.py:106-121): per-ray values, and gw[lvl] when with_grad."""
         b, R, S2 = self.buf, self.R, self.S[2]
-        self._ck(self.lib.snerf_interlevel(self._p(b["sb"][2]), self._p(b["w"][2]), S2, self._p(b["sb"][lvl]), self._p(b["w"][lvl]), self.S[lvl], R,
-                                           mult / (R * S2), self._p(b["inter_rays"][lvl]), self._p(b["gw"][lvl]) if with_grad else None, self._st), "interlevel")
+        self._call("interlevel", self._p(b["sb"][2]), self._p(b["w"][2]), S2, self._p(b["sb"][lvl]), self._p(b["w"][lvl]), self.S[lvl], R,
+                   mult / (R * S2), self._p(b["inter_rays"][lvl]), self._p(b["gw"][lvl]) if with_grad else None, self._st)

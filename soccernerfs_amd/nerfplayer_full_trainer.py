@@ -142,11 +142,11 @@ class NerfplayerFullTrainer(NerfplayerStep):
         for l, y in enumerate(outs):
             K, M = net.dims[l], net.dims[l + 1]
             if self._dense_operands:
-                self._ck(self.lib.snerf_dense_fwd_lp(self._p(net.params, woff), K, M, _ACT[acts[l]], self._p(cur, xo), ld, C.c_int64(N), self._p(y), y.stride(0),
-                                                     self._dense_operands, self._st), "dense_fwd_lp")
+                self._call("dense_fwd_lp", self._p(net.params, woff), K, M, _ACT[acts[l]], self._p(cur, xo), ld, N, self._p(y), y.stride(0),
+                           self._dense_operands, self._st)
             else:
-                self._ck(self.lib.snerf_dense_fwd(self._p(net.params, woff), K, M, _ACT[acts[l]], self._p(cur, xo), ld, C.c_int64(N), self._p(y), y.stride(0),
-                                                  self._st), "dense_fwd")
+                self._call("dense_fwd", self._p(net.params, woff), K, M, _ACT[acts[l]], self._p(cur, xo), ld, N, self._p(y), y.stride(0),
+                           self._st)
             woff += K * M
             cur, ld, xo = y, y.stride(0), 0
 
@@ -167,15 +167,17 @@ class NerfplayerFullTrainer(NerfplayerStep):
                 gx, ldgx_, go = scratch[l % 2], scratch[l % 2].stride(0), 0
             fx = self.grads_fx is not None
             if self._dense_operands:
-                self._ck(self.lib.snerf_dense_bwd_lp(
-                    self._p(net.params, woffs[l]), K, M, _ACT[acts[l]], self._p(xin, xo), ldi, C.c_int64(N), self._p(outs[l]), outs[l].stride(0), self._p(g), ldg,
+                self._call(
+                    "dense_bwd_lp",
+                    self._p(net.params, woffs[l]), K, M, _ACT[acts[l]], self._p(xin, xo), ldi, N, self._p(outs[l]), outs[l].stride(0), self._p(g), ldg,
                     self._p(gx, go) if gx is not None else None, ldgx_, None if fx else self._p(gW, woffs[l]), self._p(self.fx(gW)[woffs[l]:]) if fx else None,
-                    self._dense_operands, self._st), "dense_bwd_lp")
+                    self._dense_operands, self._st)
                 g, ldg = gx, ldgx_
                 continue
-            self._ck((self.lib.snerf_dense_bwd_fx if fx else self.lib.snerf_dense_bwd)(
-                self._p(net.params, woffs[l]), K, M, _ACT[acts[l]], self._p(xin, xo), ldi, C.c_int64(N), self._p(outs[l]), outs[l].stride(0), self._p(g), ldg,
-                self._p(gx, go) if gx is not None else None, ldgx_, self._p(self.fx(gW)[woffs[l]:]) if fx else self._p(gW, woffs[l]), self._st), "dense_bwd")
+            self._call(
+                "dense_bwd_fx" if fx else "dense_bwd",
+                self._p(net.params, woffs[l]), K, M, _ACT[acts[l]], self._p(xin, xo), ldi, N, self._p(outs[l]), outs[l].stride(0), self._p(g), ldg,
+                self._p(gx, go) if gx is not None else None, ldgx_, self._p(self.fx(gW)[woffs[l]:]) if fx else self._p(gW, woffs[l]), self._st)
             g, ldg = gx, ldgx_
 
     # ---- forward ----
@@ -201,8 +203,8 @@ class NerfplayerFullTrainer(NerfplayerStep):
         b["tN"].view(R, S).copy_(t[:, None].expand(R, S))
         self._dense_chain_fwd(self.deform, ("relu", "relu", "relu", "none"), b["x2"], 3, 0, N, b["dh"] + [b["delta"]])
         torch.add(b["x2"][:N], b["delta"], out=b["x2"][N:])                 # deformed = x + deformation_field(x) (:346)
-        self._ck(self.lib.snerf_hashgrid_encode_fwd(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), C.c_int64(2 * N), self._p(b["enc2"]),
-                                                    self._st), "hashgrid_fwd")
+        self._call("hashgrid_encode_fwd", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), 2 * N, self._p(b["enc2"]),
+                   self._st)
         b["sx"][:, :F].copy_(b["enc2"])
         b["sx"][:N, F].copy_(b["tN"])
         b["sx"][N:, F].copy_(b["tN"])                                       # cat([stationary_field(.), t]) (:349-351)
@@ -226,11 +228,11 @@ class NerfplayerFullTrainer(NerfplayerStep):
         self._tgrid_fwd(self.newness, self.newness.embeddings, self._pts, b["tN"], 1, N, b["vnew"])
         self._tgrid_fwd(self.decomp, self.decomp.embeddings, self._pts, b["tN"], 1, N, b["dfeat"])
         self._mlp_fwd(self.decomp_mlp, b["dfeat"], F, N, b["logits"], 3)
-        self._ck(self.lib.snerf_nerfplayer_mix_fwd(self._p(b["logits"]), self._p(b["sv"]), self._p(b["sv"], N * F), self._p(b["vnew"]), C.c_int64(N), F,
-                                                   self._p(b["probs"]), self._p(b["v"]), self._st), "mix_fwd")
+        self._call("nerfplayer_mix_fwd", self._p(b["logits"]), self._p(b["sv"]), self._p(b["sv"], N * F), self._p(b["vnew"]), N, F,
+                   self._p(b["probs"]), self._p(b["v"]), self._st)
         self._mlp_fwd(self.decode, b["v"], F, N, b["h"], 16, 0, b["dens"][2])   # density = trunc_exp(column 0) (:374-377)
         self._dense_chain_fwd(self.head, ("relu", "relu", "relu", "sigmoid"), b["h"], 16, 1, N, b["hh"] + [b["rgb"]])  # geo features = columns 1..15
-        self._ck(self.lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(eb), R, S, self._p(b["w"][2]), self._st), "weights_fwd")
+        self._call("weights_fwd", self._p(b["dens"][2]), self._p(eb), R, S, self._p(b["w"][2]), self._st)
         if training:
             self._render_fwd(True, 0, rng["bg"], "depth_expected")
         else:
@@ -270,9 +272,9 @@ class NerfplayerFullTrainer(NerfplayerStep):
         self._dense_chain_bwd(self.head, "field.head", ("relu", "relu", "relu", "sigmoid"), b["h"], 16, 1, N, b["hh"] + [b["rgb"]], b["grgb"], 3, b["ghh"],
                               b["gh"], 16, 1)
         self._mlp_bwd(self.decode, self.gviews["field.decode"], b["v"], F, N, b["gh"], 16, 0, b["gdens"][2], b["gv"], F)
-        self._ck(self.lib.snerf_nerfplayer_mix_bwd(self._p(b["probs"]), self._p(b["sv"]), self._p(b["sv"], N * F), self._p(b["vnew"]), self._p(b["gv"]),
-                                                   self._p(b["gprobs"]), C.c_int64(N), F, self._p(b["gsv"]), self._p(b["gsv"], N * F), self._p(b["gvnew"]),
-                                                   self._p(b["glogits"]), self._st), "mix_bwd")
+        self._call("nerfplayer_mix_bwd", self._p(b["probs"]), self._p(b["sv"]), self._p(b["sv"], N * F), self._p(b["vnew"]), self._p(b["gv"]),
+                   self._p(b["gprobs"]), N, F, self._p(b["gsv"]), self._p(b["gsv"], N * F), self._p(b["gvnew"]),
+                   self._p(b["glogits"]), self._st)
         self._mlp_bwd(self.decomp_mlp, self.gviews["field.decomp_mlp"], b["dfeat"], F, N, b["glogits"], 3, -1, None, b["gdfeat"], F)
         if self._tiled is not None and self._in_train_step:
             # owner-computes form: bin both tables' touches here (the pass reads the deformed positions), then scatter + TV + Adam per table as one pass
@@ -312,8 +314,8 @@ class NerfplayerFullTrainer(NerfplayerStep):
             # the coarse levels (every point of the batch in a handful of tiles) through the atomic kernel: table gradient from both halves ...
             th.coarse_levels(b["x2"], b["genc2"], gth, self._st)
             # ... and the coordinate gradient of the deformed half: levels [0, lc) were handled just above for the table, so one gather-only launch per range
-            self._ck(self.lib.snerf_hashgrid_encode_bwd(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), C.c_int64(N),
-                                                        self._p(b["genc2"], N * F), None, self._p(b["gx2"], 3 * N), self._st), "hashgrid_bwd (coordinates)")
+            self._call("hashgrid_encode_bwd", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), N,
+                       self._p(b["genc2"], N * F), None, self._p(b["gx2"], 3 * N), self._st)
             oh, nh = self.off["field.hash"]
             th.scatter_adam(b["x2"], b["genc2"], gth if lc > 0 else None, self.params[oh:oh + nh], self.exp_avg[oh:oh + nh], self.exp_avg_sq[oh:oh + nh], self._lr(),
                             self.step + 1, self.adam_eps, stream=self._st)
@@ -321,18 +323,17 @@ class NerfplayerFullTrainer(NerfplayerStep):
             self._hash_swept = True
         elif self.grads_fx is not None:
             gt = self._p(self.fx(self.gviews["field.hash"]))
-            self._ck(self.lib.snerf_hashgrid_encode_bwd_fx(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), C.c_int64(N), self._p(b["genc2"]),
-                                                           gt, None, self._st), "hashgrid_bwd_fx")
-            self._ck(self.lib.snerf_hashgrid_encode_bwd_fx(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), C.c_int64(N),
-                                                           self._p(b["genc2"], N * F), gt, self._p(self._gx_fx), self._st), "hashgrid_bwd_fx")
+            self._call("hashgrid_encode_bwd_fx", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), N, self._p(b["genc2"]),
+                       gt, None, self._st)
+            self._call("hashgrid_encode_bwd_fx", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), N,
+                       self._p(b["genc2"], N * F), gt, self._p(self._gx_fx), self._st)
             ops.fx_to_float(self._gx_fx, b["gx2"][N:].view(-1))  # written, cells cleared
         else:
-            self._ck(self.lib.snerf_hashgrid_encode_bwd(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), C.c_int64(N), self._p(b["genc2"]),
-                                                        self._p(self.gviews["field.hash"]), None, self._st), "hashgrid_bwd")
+            self._call("hashgrid_encode_bwd", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"]), N, self._p(b["genc2"]),
+                       self._p(self.gviews["field.hash"]), None, self._st)
             b["gx2"][N:].zero_()
-            self._ck(self.lib.snerf_hashgrid_encode_bwd(C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), C.c_int64(N),
-                                                        self._p(b["genc2"], N * F), self._p(self.gviews["field.hash"]), self._p(b["gx2"], 3 * N), self._st),
-                     "hashgrid_bwd")
+            self._call("hashgrid_encode_bwd", C.byref(self.hash.desc), self._p(self.hash.params), self._p(b["x2"], 3 * N), N,
+                       self._p(b["genc2"], N * F), self._p(self.gviews["field.hash"]), self._p(b["gx2"], 3 * N), self._st)
         self._dense_chain_bwd(self.deform, "field.deform", ("relu", "relu", "relu", "none"), b["x2"], 3, 0, N, b["dh"] + [b["delta"]], b["gx2"][N:], 3,
                               b["gdh"], None, 0)
         self._proposal_backward(t, proposal_grads)

@@ -106,17 +106,17 @@ class NerfplayerStep(FusedStep):
     # ---- temporal grids ----
     def _tgrid_fwd(self, enc, table, co, times, S, N, out):
         with self._span("tgrid_fwd.prop" if enc is self.prop_enc[0] or enc is self.prop_enc[1] else "tgrid_fwd.field"):
-            self._ck(self.lib.snerf_tgrid_encode_fwd(C.byref(enc.desc), self._p(table), C.byref(co), None, self._p(times), S, C.c_int64(N), self._p(out),
-                                                     self._st), "tgrid_fwd")
+            self._call("tgrid_encode_fwd", C.byref(enc.desc), self._p(table), C.byref(co), None, self._p(times), S, N, self._p(out),
+                       self._st)
 
     def _tgrid_bwd(self, enc, co, times, S, N, gout, gtable):
         with self._span("tgrid_bwd.prop" if enc is self.prop_enc[0] or enc is self.prop_enc[1] else "tgrid_bwd.field"):
             if self.grads_fx is not None:
-                self._ck(self.lib.snerf_tgrid_encode_bwd_fx(C.byref(enc.desc), C.byref(co), None, self._p(times), S, C.c_int64(N), self._p(gout),
-                                                            self._p(self.fx(gtable)), self._st), "tgrid_bwd_fx")
+                self._call("tgrid_encode_bwd_fx", C.byref(enc.desc), C.byref(co), None, self._p(times), S, N, self._p(gout),
+                           self._p(self.fx(gtable)), self._st)
                 return
-            self._ck(self.lib.snerf_tgrid_encode_bwd(C.byref(enc.desc), C.byref(co), None, self._p(times), S, C.c_int64(N), self._p(gout), self._p(gtable),
-                                                     self._st), "tgrid_bwd")
+            self._call("tgrid_encode_bwd", C.byref(enc.desc), C.byref(co), None, self._p(times), S, N, self._p(gout), self._p(gtable),
+                       self._st)
 
     def _tv_sign(self, k: int):
         """Value + per-row signed step of table k's temporal TV; the row draw is the reference's randint."""
@@ -125,8 +125,8 @@ class NerfplayerStep(FusedStep):
         ca, cb = enc._index_list_host[row]
         self._tv_cols[k] = (ca, cb)
         rows_, gc = enc.embeddings.shape
-        self._ck(self.lib.snerf_tgrid_tv_sign(self._p(enc.embeddings), C.c_int64(rows_), gc, ca, cb, float(self.cfg.temporal_tv_weight) * self.TV_SCALE,
-                                              self._p(self.buf["tv"][k]), 64, self._p(self._srow[k]), self._st), "tv_sign")
+        self._call("tgrid_tv_sign", self._p(enc.embeddings), rows_, gc, ca, cb, float(self.cfg.temporal_tv_weight) * self.TV_SCALE,
+                   self._p(self.buf["tv"][k]), 64, self._p(self._srow[k]), self._st)
 
     def _tv_early(self, stream, ks):
         """The TV passes of tables `ks` read parameters only: on a side stream at the START of the backward, beside it, instead of on the caller's
@@ -163,9 +163,9 @@ class NerfplayerStep(FusedStep):
         ca, cb = self._tv_cols[k]
         rows_, gc = self._encs[k].embeddings.shape
         with self._span("adam_tv." + self._enc_names[k]):
-            self._ck(self.lib.snerf_adam_step_tv(self._p(self.params[sl]), self._p(self.grads[sl]), self._p(self.exp_avg[sl]), self._p(self.exp_avg_sq[sl]),
-                                                 C.c_int64(rows_), gc, ca, cb, self._p(self._srow[k]), lr, 0.9, 0.999, self.adam_eps, self.step + 1, 1.0, 1,
-                                                 None, st), "adam_step_tv")
+            self._call("adam_step_tv", self._p(self.params[sl]), self._p(self.grads[sl]), self._p(self.exp_avg[sl]), self._p(self.exp_avg_sq[sl]),
+                       rows_, gc, ca, cb, self._p(self._srow[k]), lr, 0.9, 0.999, self.adam_eps, self.step + 1, 1.0, 1,
+                       None, st)
 
     def _early_table_sweeps(self, ks):
         """The Adam sweeps of tables `ks` on the side stream, behind everything the caller's stream holds (their gradient scatters) and behind their

@@ -153,15 +153,15 @@ class NerfplayerTrainer(NerfplayerStep):
         else:
             app, cm = None, None
         dd = d if d.is_contiguous() else d.contiguous()
-        self._ck(self.lib.snerf_nerfacto_head_input_fwd(self._p(dd), self._p(b["h"]), self._p(app) if app is not None else None,
-                                                        self._p(cm) if cm is not None else None, S, R, self._p(b["hx"]), self._st), "head_input_fwd")
+        self._call("nerfacto_head_input_fwd", self._p(dd), self._p(b["h"]), self._p(app) if app is not None else None,
+                   self._p(cm) if cm is not None else None, S, R, self._p(b["hx"]), self._st)
         self._mlp_fwd(self.head, b["hx"], 64, N, b["rgb"], 3)
         self._ray_deferred = bool(training and self._in_train_step and self.fused_ray_loss)
         if self._ray_deferred:
             # train_step: weights, compositing, MSE backward, distortion and the weights' backward are ONE launch at the start of backward()
             # (snerf_ray_train_fwd_bwd, bit-identical to the five kernels); the expected depth (an output no loss of this model reads) is not rendered
             return b["rgb_out"]
-        self._ck(self.lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), R, S, self._p(b["w"][2]), self._st), "weights_fwd")
+        self._call("weights_fwd", self._p(b["dens"][2]), self._p(b["eb"][2]), R, S, self._p(b["w"][2]), self._st)
         self._render_fwd(training, 0, rng["bg"], "depth_expected")
         return b["rgb_out"]
 
@@ -190,9 +190,9 @@ class NerfplayerTrainer(NerfplayerStep):
         # gh[:, 1:16] = ghx[:, 16:31] (column 0, the density, enters through gaux below); appearance gradient = per-ray sums of ghx[:, 31:63] added to the
         # cameras' rows -- fixed-point cells in deterministic mode
         fx = self.grads_fx is not None
-        self._ck(self.lib.snerf_nerfacto_head_input_bwd(self._p(b["ghx"]), self._p(self.cams), S2, R, self._p(b["gh"]),
-                                                        None if fx else self._p(self.gviews["field.appearance"]),
-                                                        self._p(self.fxviews["field.appearance"]) if fx else None, self._st), "head_input_bwd")
+        self._call("nerfacto_head_input_bwd", self._p(b["ghx"]), self._p(self.cams), S2, R, self._p(b["gh"]),
+                   None if fx else self._p(self.gviews["field.appearance"]),
+                   self._p(self.fxviews["field.appearance"]) if fx else None, self._st)
         self._mlp_bwd(self.decode, self.gviews["field.decode"], b["feat"], self.enc.output_dim, N2, b["gh"], 16, 0, b["gdens"][2], b["gfeat"],
                       self.enc.output_dim)
         if self._tiled is not None and self._in_train_step:

@@ -70,8 +70,7 @@ class _KPlanesGather(torch.autograd.Function):
         """pts: the points tensor itself (coords mode 0) when it asks for a gradient -- the camera optimiser's path; None otherwise."""
         out = torch.empty(N, ps.out_dim, dtype=torch.float32, device=planes.device)
         desc = ps.space_desc() if freeze & 1 else ps.desc()
-        _lib.check(_lib.lib().snerf_kplanes_gather_fwd(C.byref(desc), _ptr(planes), C.byref(coords), C.c_int64(N), _ptr(out), _stream()),
-                   "kplanes_gather_fwd")
+        _lib.call("kplanes_gather_fwd", C.byref(desc), _ptr(planes), C.byref(coords), N, _ptr(out), _stream())
         ctx.ps, ctx.coords, ctx.keep, ctx.N, ctx.freeze, ctx.desc = ps, coords, coords_keepalive, N, freeze, desc
         ctx.save_for_backward(planes)
         return out
@@ -89,8 +88,8 @@ class _KPlanesGather(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None, gpts
         gplanes = torch.zeros_like(planes)
-        _lib.check(_lib.lib().snerf_kplanes_gather_bwd(C.byref(ctx.desc), _ptr(planes), C.byref(ctx.coords), C.c_int64(ctx.N), _ptr(gout),
-                                                       _ptr(gplanes), _stream()), "kplanes_gather_bwd")
+        _lib.call("kplanes_gather_bwd", C.byref(ctx.desc), _ptr(planes), C.byref(ctx.coords), ctx.N, _ptr(gout),
+                  _ptr(gplanes), _stream())
         if ctx.freeze & 2:
             for s in range(len(ps.resolutions)):
                 gplanes[ps.offsets[s][0]: ps.offsets[s][4]].zero_()  # XY XZ XT YZ are contiguous in the buffer
@@ -114,11 +113,11 @@ def kplanes_gather_bwd_coords(desc: _lib.KPlanesDesc, planes, coords: _lib.Coord
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (R, 3):
             raise RuntimeError(f"kplanes_gather_bwd_coords: {name} must be a contiguous float32 HIP tensor [{R}, 3]")
     gpts = torch.empty(N, desc.n_coords, dtype=torch.float32, device=grad_out.device) if want_pts else None
-    _lib.check(_lib.lib().snerf_kplanes_gather_bwd_coords(C.byref(desc), _ptr(planes), C.byref(coords), C.c_int64(N), _ptr(grad_out),
-                                                          _ptr(gpts) if gpts is not None else None,
-                                                          _ptr(grad_origins) if grad_origins is not None else None,
-                                                          _ptr(grad_dirs) if grad_dirs is not None else None,
-                                                          stream if stream is not None else _stream()), "kplanes_gather_bwd_coords")
+    _lib.call("kplanes_gather_bwd_coords", C.byref(desc), _ptr(planes), C.byref(coords), N, _ptr(grad_out),
+              _ptr(gpts) if gpts is not None else None,
+              _ptr(grad_origins) if grad_origins is not None else None,
+              _ptr(grad_dirs) if grad_dirs is not None else None,
+              stream if stream is not None else _stream())
     return {"grad_pts": gpts}
 
 
@@ -135,14 +134,15 @@ class SortedScatter:
             raise ValueError("gvec_dtype must be torch.float32 or torch.bfloat16")
         self.ps, self.N, self.desc = ps, N, ps.desc() if desc is None else desc
         self.gvec_bf16 = int(gvec_dtype == torch.bfloat16)
-        hc, ie = C.c_int64(0), C.c_int64(0)
-        _lib.check(_lib.lib().snerf_kplanes_sort_workspace(C.byref(self.desc), C.c_int64(N), C.byref(hc), C.byref(ie)), "sort_workspace")
-        self.hist = torch.empty(hc.value, dtype=torch.int32, device=device)
-        self.rank = torch.empty(ie.value, dtype=torch.int32, device=device)
-        self.sorted_rec = torch.empty(ie.value, 4, dtype=torch.float32, device=device)  # {sample id bits, pixel x, pixel y, 0}
+        sizes = (C.c_int64 * 2)()  # hist_cells, index_elems
+        _lib.call("kplanes_sort_workspace", C.byref(self.desc), N, sizes, C.byref(sizes, 8))
+        hist_cells, index_elems = sizes
+        self.hist = torch.empty(hist_cells, dtype=torch.int32, device=device)
+        self.rank = torch.empty(index_elems, dtype=torch.int32, device=device)
+        self.sorted_rec = torch.empty(index_elems, 4, dtype=torch.float32, device=device)  # {sample id bits, pixel x, pixel y, 0}
         self.quotient = bool(quotient)
         if self.quotient:
-            if not _lib.lib().snerf_kplanes_quotient_supported(C.byref(self.desc), C.c_int64(N)):
+            if not _lib.lib().snerf_kplanes_quotient_supported(C.byref(self.desc), N):
                 raise ValueError("the quotient scatter is built for C = 32, concatenated scales and N * 32 * n_scales < 2^31")
             rows = N * len(ps.resolutions)
             self.G = torch.empty(N, ps.out_dim, dtype=torch.float32, device=device)       # gfeat .* feat
@@ -161,18 +161,16 @@ class SortedScatter:
             self.fix_count = self.fix_counts[0:1]
             self.gvec = None
         else:
-            self.gvec = torch.empty(len(ps.resolutions) * ie.value * ps.C, dtype=gvec_dtype, device=device)  # [scale*planes+plane][N][C]
+            self.gvec = torch.empty(len(ps.resolutions) * index_elems * ps.C, dtype=gvec_dtype, device=device)  # [scale*planes+plane][N][C]
 
     def sort(self, coords: _lib.Coords, stream=None):
-        _lib.check(_lib.lib().snerf_kplanes_sort_samples(C.byref(self.desc), C.byref(coords), C.c_int64(self.N), _ptr(self.hist), _ptr(self.rank),
-                                                         _ptr(self.sorted_rec), stream if stream is not None else _stream()), "sort_samples")
+        _lib.call("kplanes_sort_samples", C.byref(self.desc), C.byref(coords), self.N, _ptr(self.hist), _ptr(self.rank),
+                  _ptr(self.sorted_rec), stream if stream is not None else _stream())
 
     def scatter(self, planes, coords: _lib.Coords, gout, gplanes, stream=None):
         st = stream if stream is not None else _stream()
-        _lib.check(_lib.lib().snerf_kplanes_gradvec(C.byref(self.desc), _ptr(planes), C.byref(coords), C.c_int64(self.N), _ptr(gout), _ptr(self.gvec), self.gvec_bf16, st),
-                   "gradvec")
-        _lib.check(_lib.lib().snerf_kplanes_scatter_sorted(C.byref(self.desc), C.c_int64(self.N), _ptr(self.gvec), self.gvec_bf16, _ptr(self.sorted_rec), _ptr(gplanes), st),
-                   "scatter_sorted")
+        _lib.call("kplanes_gradvec", C.byref(self.desc), _ptr(planes), C.byref(coords), self.N, _ptr(gout), _ptr(self.gvec), self.gvec_bf16, st)
+        _lib.call("kplanes_scatter_sorted", C.byref(self.desc), self.N, _ptr(self.gvec), self.gvec_bf16, _ptr(self.sorted_rec), _ptr(gplanes), st)
 
 
     # ---- quotient form: g_q = (gfeat .* feat) ./ v_q (include/snerf.h) ----
@@ -187,18 +185,16 @@ class SortedScatter:
     def quotient_prepare(self, gfeat, feat, stream=None):
         st = stream if stream is not None else _stream()
         k = self.next_fix_counter()
-        _lib.check(_lib.lib().snerf_kplanes_quotient_prepare(C.byref(self.desc), C.c_int64(self.N), _ptr(gfeat), _ptr(feat), _ptr(self.G), _ptr(self.fix_list),
-                                                             self.fix_capacity, _ptr(self.fix_count), _ptr(self.fix_counts[1 - k:2 - k]), st),
-                   "quotient_prepare")
+        _lib.call("kplanes_quotient_prepare", C.byref(self.desc), self.N, _ptr(gfeat), _ptr(feat), _ptr(self.G), _ptr(self.fix_list),
+                  self.fix_capacity, _ptr(self.fix_count), _ptr(self.fix_counts[1 - k:2 - k]), st)
 
     def quotient_fixup_scales(self, planes, coords: _lib.Coords, gplanes, scale_begin: int, scale_end: int, stream=None):
         """The exact terms of the listed (vanished-feature) elements for scales [scale_begin, scale_end): reads the sample coordinates, so it belongs on
         the stream that owns the ray buffers."""
         st = stream if stream is not None else _stream()
-        _lib.check(_lib.lib().snerf_kplanes_quotient_fixup(C.byref(self.desc), _ptr(planes), C.byref(coords), C.c_int64(self.N), _ptr(self.fix_list),
-                                                           _ptr(self.fix_count), self.fix_capacity, _ptr(gplanes), scale_begin, scale_end,
-                                                           _ptr(self.fix_peak), st),
-                   "quotient_fixup")
+        _lib.call("kplanes_quotient_fixup", C.byref(self.desc), _ptr(planes), C.byref(coords), self.N, _ptr(self.fix_list),
+                  _ptr(self.fix_count), self.fix_capacity, _ptr(gplanes), scale_begin, scale_end,
+                  _ptr(self.fix_peak), st)
 
     def check_fix_overflow(self, peak: Optional[int] = None):
         """Raises if a fix-up ever found more listed entries than the list holds (their gradient terms were lost).  Reads the device
@@ -221,8 +217,8 @@ class SortedScatter:
     def quotient_pass_b_scales(self, planes, gplanes, scale_begin: int, scale_end: int, stream=None):
         """Pass B for scales [scale_begin, scale_end): reads only the sorted records, G and the planes -- never the ray buffers."""
         st = stream if stream is not None else _stream()
-        _lib.check(_lib.lib().snerf_kplanes_scatter_quotient_scales(C.byref(self.desc), _ptr(planes), C.c_int64(self.N), _ptr(self.G), _ptr(self.sorted_rec),
-                                                                    _ptr(gplanes), scale_begin, scale_end, st), "scatter_quotient")
+        _lib.call("kplanes_scatter_quotient_scales", C.byref(self.desc), _ptr(planes), self.N, _ptr(self.G), _ptr(self.sorted_rec),
+                  _ptr(gplanes), scale_begin, scale_end, st)
 
     def quotient_scatter_scales(self, planes, coords: _lib.Coords, gfeat, gplanes, scale_begin: int, scale_end: int, stream=None):
         """Fix-up + pass B for scales [scale_begin, scale_end); G and the fix list must have been produced (quotient_prepare, or the sigma_net backward's
@@ -280,8 +276,8 @@ def spaced_bins(nears, fars, num_samples: int, t_rand=None, kind: str = "uniform
     if t_rand is not None:
         t_rand = _f32c(t_rand, "t_rand")
         cols = t_rand.shape[-1]
-    _lib.check(_lib.lib().snerf_spaced_bins(_ptr(nears), _ptr(fars), _ptr(t_rand) if t_rand is not None else None, cols, R, S,
-                                            SPACING_KIND[kind], _ptr(sb), _ptr(eb), _stream()), "spaced_bins")
+    _lib.call("spaced_bins", _ptr(nears), _ptr(fars), _ptr(t_rand) if t_rand is not None else None, cols, R, S,
+              SPACING_KIND[kind], _ptr(sb), _ptr(eb), _stream())
     return sb, eb
 
 
@@ -290,7 +286,7 @@ class _Weights(torch.autograd.Function):
     def forward(ctx, density, ebins):
         R, S = density.shape
         w = torch.empty_like(density)
-        _lib.check(_lib.lib().snerf_weights_fwd(_ptr(density), _ptr(ebins), R, S, _ptr(w), _stream()), "weights_fwd")
+        _lib.call("weights_fwd", _ptr(density), _ptr(ebins), R, S, _ptr(w), _stream())
         ctx.save_for_backward(density, ebins)
         return w
 
@@ -300,7 +296,7 @@ class _Weights(torch.autograd.Function):
         R, S = density.shape
         gw = gw.contiguous()
         gd = torch.empty_like(density)
-        _lib.check(_lib.lib().snerf_weights_bwd(_ptr(density), _ptr(ebins), _ptr(gw), R, S, _ptr(gd), 0, None, _stream()), "weights_bwd")
+        _lib.call("weights_bwd", _ptr(density), _ptr(ebins), _ptr(gw), R, S, _ptr(gd), 0, None, _stream())
         return gd, None
 
 
@@ -349,7 +345,7 @@ def pdf_resample(sbins_prev, nears, fars, num_samples: int, weights=None, densit
     a.inds_out = inds.data_ptr() if inds is not None else None
     a.R, a.S_prev, a.S, a.kind = R, Sp, S, SPACING_KIND[kind]
     a.anneal, a.histogram_padding, a.eps = anneal, histogram_padding, eps
-    _lib.check(_lib.lib().snerf_pdf_resample(C.byref(a), _stream()), "pdf_resample")
+    _lib.call("pdf_resample", C.byref(a), _stream())
     out = [sb, eb]
     if return_inds:
         out.append(inds)
@@ -367,8 +363,8 @@ class _MLP(torch.autograd.Function):
         N = x.shape[0]
         y = torch.empty(N, desc.d_out, dtype=torch.float32, device=x.device)
         aux = torch.empty(N, dtype=torch.float32, device=x.device) if aux_col >= 0 else None
-        _lib.check(_lib.lib().snerf_mlp_fwd(C.byref(desc), _ptr(params), _ptr(x), x.stride(0), C.c_int64(N), _ptr(y), desc.d_out,
-                                            aux_col, _ptr(aux) if aux is not None else None, _stream()), "mlp_fwd")
+        _lib.call("mlp_fwd", C.byref(desc), _ptr(params), _ptr(x), x.stride(0), N, _ptr(y), desc.d_out,
+                  aux_col, _ptr(aux) if aux is not None else None, _stream())
         ctx.desc, ctx.aux_col, ctx.need_gx = desc, aux_col, need_gx
         ctx.save_for_backward(x, params)
         if aux is None:
@@ -384,10 +380,10 @@ class _MLP(torch.autograd.Function):
         gaux = gaux.contiguous() if gaux is not None else None
         gx = torch.empty(N, desc.d_in, dtype=torch.float32, device=x.device) if ctx.need_gx else None
         gw = torch.zeros_like(params)
-        _lib.check(_lib.lib().snerf_mlp_bwd(C.byref(desc), _ptr(params), _ptr(x), x.stride(0), C.c_int64(N),
-                                            _ptr(gy) if gy is not None else None, desc.d_out, ctx.aux_col,
-                                            _ptr(gaux) if gaux is not None else None,
-                                            _ptr(gx) if gx is not None else None, desc.d_in, _ptr(gw), _stream()), "mlp_bwd")
+        _lib.call("mlp_bwd", C.byref(desc), _ptr(params), _ptr(x), x.stride(0), N,
+                  _ptr(gy) if gy is not None else None, desc.d_out, ctx.aux_col,
+                  _ptr(gaux) if gaux is not None else None,
+                  _ptr(gx) if gx is not None else None, desc.d_in, _ptr(gw), _stream())
         return gx, gw, None, None, None
 
 
@@ -410,17 +406,16 @@ class _DenseNet(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, params, dims, acts, operands=0):
         N = x.shape[0]
-        l = _lib.lib()
         saved, h, off = [x], x, 0
         for i in range(len(dims) - 1):
             K, M = dims[i], dims[i + 1]
             y = torch.empty(N, M, dtype=torch.float32, device=x.device)
             if operands:  # 16-bit MFMA operands (csrc/dense_lp.hip)
-                _lib.check(l.snerf_dense_fwd_lp(C.c_void_p(params.data_ptr() + 4 * off), K, M, acts[i], _ptr(h), h.stride(0), C.c_int64(N), _ptr(y), M,
-                                                operands, _stream()), "dense_fwd_lp")
+                _lib.call("dense_fwd_lp", params.data_ptr() + 4 * off, K, M, acts[i], _ptr(h), h.stride(0), N, _ptr(y), M,
+                          operands, _stream())
             else:
-                _lib.check(l.snerf_dense_fwd(C.c_void_p(params.data_ptr() + 4 * off), K, M, acts[i], _ptr(h), h.stride(0), C.c_int64(N), _ptr(y), M,
-                                             _stream()), "dense_fwd")
+                _lib.call("dense_fwd", params.data_ptr() + 4 * off, K, M, acts[i], _ptr(h), h.stride(0), N, _ptr(y), M,
+                          _stream())
             saved.append(y)
             h = y
             off += K * M
@@ -433,8 +428,7 @@ class _DenseNet(torch.autograd.Function):
         params, *saved = ctx.saved_tensors
         dims, acts = ctx.dims, ctx.acts
         N = saved[0].shape[0]
-        l = _lib.lib()
-        gw = torch.zeros_like(params)
+        gw =torch.zeros_like(params)
         offs = [0]
         for i in range(len(dims) - 1):
             offs.append(offs[-1] + dims[i] * dims[i + 1])
@@ -445,13 +439,12 @@ class _DenseNet(torch.autograd.Function):
             need_gx = i > 0 or ctx.needs_input_grad[0]
             gx = torch.empty(N, K, dtype=torch.float32, device=g.device) if need_gx else None
             if ctx.operands:
-                _lib.check(l.snerf_dense_bwd_lp(C.c_void_p(params.data_ptr() + 4 * offs[i]), K, M, acts[i], _ptr(x), x.stride(0), C.c_int64(N), _ptr(y), M,
-                                                _ptr(g), M, _ptr(gx) if gx is not None else None, K, C.c_void_p(gw.data_ptr() + 4 * offs[i]), None,
-                                                ctx.operands, _stream()), "dense_bwd_lp")
+                _lib.call("dense_bwd_lp", params.data_ptr() + 4 * offs[i], K, M, acts[i], _ptr(x), x.stride(0), N, _ptr(y), M,
+                          _ptr(g), M, _ptr(gx) if gx is not None else None, K, gw.data_ptr() + 4 * offs[i], None,
+                          ctx.operands, _stream())
             else:
-                _lib.check(l.snerf_dense_bwd(C.c_void_p(params.data_ptr() + 4 * offs[i]), K, M, acts[i], _ptr(x), x.stride(0), C.c_int64(N), _ptr(y), M,
-                                             _ptr(g), M, _ptr(gx) if gx is not None else None, K, C.c_void_p(gw.data_ptr() + 4 * offs[i]), _stream()),
-                           "dense_bwd")
+                _lib.call("dense_bwd", params.data_ptr() + 4 * offs[i], K, M, acts[i], _ptr(x), x.stride(0), N, _ptr(y), M,
+                          _ptr(g), M, _ptr(gx) if gx is not None else None, K, gw.data_ptr() + 4 * offs[i], _stream())
             g = gx
         return g, gw, None, None, None
 
@@ -475,7 +468,7 @@ class _TruncExp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         y = torch.empty_like(x)
-        _lib.check(_lib.lib().snerf_trunc_exp_fwd(_ptr(x), x.numel(), _ptr(y), _stream()), "trunc_exp_fwd")
+        _lib.call("trunc_exp_fwd", _ptr(x), x.numel(), _ptr(y), _stream())
         ctx.save_for_backward(x)
         return y
 
@@ -484,7 +477,7 @@ class _TruncExp(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         g = g.contiguous()
         gx = torch.empty_like(x)
-        _lib.check(_lib.lib().snerf_trunc_exp_bwd(_ptr(x), _ptr(g), x.numel(), _ptr(gx), _stream()), "trunc_exp_bwd")
+        _lib.call("trunc_exp_bwd", _ptr(x), _ptr(g), x.numel(), _ptr(gx), _stream())
         return gx
 
 
@@ -499,7 +492,7 @@ class _BasisRgb(torch.autograd.Function):
     def forward(ctx, feat, basis):
         N, F = feat.shape
         rgb = torch.empty(N, 3, dtype=torch.float32, device=feat.device)
-        _lib.check(_lib.lib().snerf_basis_rgb_fwd(_ptr(feat), feat.stride(0), _ptr(basis), N, F, _ptr(rgb), _stream()), "basis_rgb_fwd")
+        _lib.call("basis_rgb_fwd", _ptr(feat), feat.stride(0), _ptr(basis), N, F, _ptr(rgb), _stream())
         ctx.save_for_backward(feat, basis, rgb)
         return rgb
 
@@ -510,8 +503,8 @@ class _BasisRgb(torch.autograd.Function):
         g = g.contiguous()
         gf = torch.empty(N, F, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(basis)
-        _lib.check(_lib.lib().snerf_basis_rgb_bwd(_ptr(feat), feat.stride(0), _ptr(basis), _ptr(rgb), _ptr(g), N, F, _ptr(gf) if gf is not None else None,
-                                                  _ptr(gb), _stream()), "basis_rgb_bwd")
+        _lib.call("basis_rgb_bwd", _ptr(feat), feat.stride(0), _ptr(basis), _ptr(rgb), _ptr(g), N, F, _ptr(gf) if gf is not None else None,
+                  _ptr(gb), _stream())
         return gf, gb
 
 
@@ -542,7 +535,7 @@ class _HashGrid(torch.autograd.Function):
     def forward(ctx, x, table, desc):
         B = x.shape[0]
         out = torch.empty(B, desc.L * desc.F, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().snerf_hashgrid_encode_fwd(C.byref(desc), _ptr(table), _ptr(x), C.c_int64(B), _ptr(out), _stream()), "hashgrid_encode_fwd")
+        _lib.call("hashgrid_encode_fwd", C.byref(desc), _ptr(table), _ptr(x), B, _ptr(out), _stream())
         ctx.desc = desc
         ctx.save_for_backward(x, table)
         return out
@@ -555,9 +548,8 @@ class _HashGrid(torch.autograd.Function):
         gx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
         if gt is None and gx is None:
             return None, None, None
-        _lib.check(_lib.lib().snerf_hashgrid_encode_bwd(C.byref(ctx.desc), _ptr(table), _ptr(x), C.c_int64(x.shape[0]), _ptr(g),
-                                                        _ptr(gt) if gt is not None else None, _ptr(gx) if gx is not None else None, _stream()),
-                   "hashgrid_encode_bwd")
+        _lib.call("hashgrid_encode_bwd", C.byref(ctx.desc), _ptr(table), _ptr(x), x.shape[0], _ptr(g),
+                  _ptr(gt) if gt is not None else None, _ptr(gx) if gx is not None else None, _stream())
         return gx, gt, None
 
 
@@ -610,7 +602,7 @@ class _Render(torch.autograd.Function):
         a.R, a.S, a.bg_mode, a.training = R, S, bg_mode, int(training)
         a.rgb_out, a.acc_out, a.depth_median, a.depth_expected = out.data_ptr(), acc.data_ptr(), dmed.data_ptr(), dexp.data_ptr()
         a.median_rgb, a.median_index = mrgb.data_ptr(), midx.data_ptr()
-        _lib.check(_lib.lib().snerf_render_fwd(C.byref(a), _stream()), "render_fwd")
+        _lib.call("render_fwd", C.byref(a), _stream())
         ctx.bg_mode = bg_mode
         ctx.save_for_backward(weights, rgb, bg if bg is not None else weights.new_zeros(3))
         ctx.mark_non_differentiable(dmed, dexp, mrgb, midx)
@@ -626,9 +618,8 @@ class _Render(torch.autograd.Function):
         gw = torch.empty_like(weights)
         grgb = torch.empty_like(rgb)
         g_acc_p = g_acc.contiguous() if g_acc is not None else None
-        _lib.check(_lib.lib().snerf_render_bwd(_ptr(weights), _ptr(rgb), _ptr(bg), ctx.bg_mode, _ptr(g_out),
-                                               _ptr(g_acc_p) if g_acc_p is not None else None, R, S, _ptr(gw), _ptr(grgb), 0, _stream()),
-                   "render_bwd")
+        _lib.call("render_bwd", _ptr(weights), _ptr(rgb), _ptr(bg), ctx.bg_mode, _ptr(g_out),
+                  _ptr(g_acc_p) if g_acc_p is not None else None, R, S, _ptr(gw), _ptr(grgb), 0, _stream())
         return gw, grgb, None, None, None, None
 
 
@@ -647,7 +638,7 @@ class _Distortion(torch.autograd.Function):
         R, S = weights.shape
         loss_rays = torch.empty(R, dtype=torch.float32, device=weights.device)
         gw = torch.empty_like(weights)
-        _lib.check(_lib.lib().snerf_distortion(_ptr(weights), _ptr(sbins), R, S, 1.0 / R, _ptr(loss_rays), _ptr(gw), 0, _stream()), "distortion")
+        _lib.call("distortion", _ptr(weights), _ptr(sbins), R, S, 1.0 / R, _ptr(loss_rays), _ptr(gw), 0, _stream())
         ctx.save_for_backward(gw)
         return loss_rays.mean()
 
@@ -669,8 +660,8 @@ class _Interlevel(torch.autograd.Function):
         S = w_nerf.shape[1]
         loss_rays = torch.empty(R, dtype=torch.float32, device=w_prop.device)
         g = torch.empty_like(w_prop)
-        _lib.check(_lib.lib().snerf_interlevel(_ptr(c_bins), _ptr(w_nerf), S, _ptr(p_bins), _ptr(w_prop), Sp, R, 1.0 / (R * S),
-                                               _ptr(loss_rays), _ptr(g), _stream()), "interlevel")
+        _lib.call("interlevel", _ptr(c_bins), _ptr(w_nerf), S, _ptr(p_bins), _ptr(w_prop), Sp, R, 1.0 / (R * S),
+                  _ptr(loss_rays), _ptr(g), _stream())
         ctx.save_for_backward(g)
         return loss_rays.sum() / (R * S)
 
@@ -696,8 +687,8 @@ class _DepthLoss(torch.autograd.Function):
         R, S = weights.shape
         loss_rays = torch.empty(R, dtype=torch.float32, device=weights.device)
         gw = torch.empty_like(weights)
-        _lib.check(_lib.lib().snerf_depth_loss(_ptr(weights), _ptr(ebins), _ptr(term), _ptr(dnorm) if dnorm is not None else None, sigma, R, S, 1.0 / R,
-                                               _ptr(loss_rays), _ptr(gw), 0, _stream()), "depth_loss")
+        _lib.call("depth_loss", _ptr(weights), _ptr(ebins), _ptr(term), _ptr(dnorm) if dnorm is not None else None, sigma, R, S, 1.0 / R,
+                  _ptr(loss_rays), _ptr(gw), 0, _stream())
         ctx.save_for_backward(gw)
         return loss_rays.mean()
 
@@ -721,8 +712,8 @@ class _UrfDepthLoss(torch.autograd.Function):
         R, S = weights.shape
         loss_rays = torch.empty(R, dtype=torch.float32, device=weights.device)
         gw, gp = torch.empty_like(weights), torch.empty(R, dtype=torch.float32, device=weights.device)
-        _lib.check(_lib.lib().snerf_urf_depth_loss(_ptr(weights), _ptr(ebins), _ptr(term), _ptr(dnorm) if dnorm is not None else None, _ptr(pred), sigma, R, S,
-                                                   1.0 / R, _ptr(loss_rays), _ptr(gw), _ptr(gp), 0, _stream()), "urf_depth_loss")
+        _lib.call("urf_depth_loss", _ptr(weights), _ptr(ebins), _ptr(term), _ptr(dnorm) if dnorm is not None else None, _ptr(pred), sigma, R, S,
+                  1.0 / R, _ptr(loss_rays), _ptr(gw), _ptr(gp), 0, _stream())
         ctx.save_for_backward(gw, gp)
         ctx.pred_shape = pred.shape
         return loss_rays.mean()
@@ -749,7 +740,7 @@ class _PlaneReg(torch.autograd.Function):
     def forward(ctx, planes, ps: PlaneSet):
         parts = torch.zeros(REG_SLOTS, 16, dtype=torch.float32, device=planes.device)
         desc = ps.desc()
-        _lib.check(_lib.lib().snerf_plane_reg(C.byref(desc), _ptr(planes), None, 0.0, 0.0, 0.0, _ptr(parts), REG_SLOTS, 0, _stream()), "plane_reg")
+        _lib.call("plane_reg", C.byref(desc), _ptr(planes), None, 0.0, 0.0, 0.0, _ptr(parts), REG_SLOTS, 0, _stream())
         ctx.ps = ps
         ctx.save_for_backward(planes)
         return parts[:, :3].sum(0)
@@ -760,7 +751,7 @@ class _PlaneReg(torch.autograd.Function):
         c = g.detach().cpu().tolist()  # three coefficients (host sync; the fused trainer passes them directly)
         grad = torch.empty_like(planes)  # overwrite mode: every element of every plane is written
         desc = ctx.ps.desc()
-        _lib.check(_lib.lib().snerf_plane_reg(C.byref(desc), _ptr(planes), _ptr(grad), c[0], c[1], c[2], None, 0, 1, _stream()), "plane_reg")
+        _lib.call("plane_reg", C.byref(desc), _ptr(planes), _ptr(grad), c[0], c[1], c[2], None, 0, 1, _stream())
         return grad, None
 
 
@@ -778,8 +769,8 @@ def new_adam_dyn(device) -> torch.Tensor:
 def adam_prepare(dyn: torch.Tensor, lr: float, betas=(0.9, 0.999), policy: str = "skip_step", force_nonfinite: bool = False):
     """Once per parameter group and step, before its Adam kernels: decides whether the step is skipped (GradScaler semantics,
     NS/engine/trainer.py:394-408), advances the device-side step counter and the bias corrections."""
-    _lib.check(_lib.lib().snerf_adam_prepare(_ptr(dyn), lr, betas[0], betas[1], {"drop_elements": 0, "skip_step": 1}[policy], int(force_nonfinite),
-                                             _stream()), "adam_prepare")
+    _lib.call("adam_prepare", _ptr(dyn), lr, betas[0], betas[1], {"drop_elements": 0, "skip_step": 1}[policy], int(force_nonfinite),
+              _stream())
 
 
 def adam_step(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-12, grad_scale: float = 1.0, zero_grad: bool = False,
@@ -788,8 +779,8 @@ def adam_step(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps: float =
     (adam_prepare) -- `step` is then ignored."""
     for t in (p, g, m, v):
         _f32c(t, "adam buffer")
-    _lib.check(_lib.lib().snerf_adam_step(_ptr(p), _ptr(p if p_out is None else p_out), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps,
-                                          step, grad_scale, int(zero_grad), _ptr(dyn) if dyn is not None else None, _stream()), "adam_step")
+    _lib.call("adam_step", _ptr(p), _ptr(p if p_out is None else p_out), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps,
+              step, grad_scale, int(zero_grad), _ptr(dyn) if dyn is not None else None, _stream())
 
 
 def adam_planes_step(ps: PlaneSet, p_in, p_out, g, m, v, coefs, losses, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-12,
@@ -801,18 +792,17 @@ def adam_planes_step(ps: PlaneSet, p_in, p_out, g, m, v, coefs, losses, step: in
     moments and their gradients untouched (the kernel locates its workgroups per plane, and the view's offsets are monotone)."""
     desc = ps.desc() if desc is None else desc
     lo, hi = (0, ps.numel + 3 & ~3) if shard_range is None else shard_range
-    _lib.check(_lib.lib().snerf_adam_planes_step_range(C.byref(desc), _ptr(p_in), _ptr(p_out), _ptr(g), _ptr(m), _ptr(v), coefs[0], coefs[1], coefs[2],
-                                                       _ptr(losses) if losses is not None else None, REG_SLOTS if losses is not None else 0, lr,
-                                                       betas[0], betas[1], eps, step, grad_scale, int(zero_grad), int(lo), int(hi),
-                                                       _ptr(dyn) if dyn is not None else None, _stream()),
-               "adam_planes_step")
+    _lib.call("adam_planes_step_range", C.byref(desc), _ptr(p_in), _ptr(p_out), _ptr(g), _ptr(m), _ptr(v), coefs[0], coefs[1], coefs[2],
+              _ptr(losses) if losses is not None else None, REG_SLOTS if losses is not None else 0, lr,
+              betas[0], betas[1], eps, step, grad_scale, int(zero_grad), int(lo), int(hi),
+              _ptr(dyn) if dyn is not None else None, _stream())
 
 
 def fx_to_float(fx: torch.Tensor, out: torch.Tensor, accumulate: bool = False):
     """Deterministic mode: fixed-point gradient cells (int64, value * 2^50) -> float gradients; clears the cells."""
     if fx.dtype != torch.int64 or out.dtype != torch.float32 or fx.numel() != out.numel():
         raise RuntimeError("fx_to_float: need an int64 cell buffer and a float32 buffer of the same length")
-    _lib.check(_lib.lib().snerf_fx_to_float(_ptr(fx), _ptr(out), fx.numel(), int(accumulate), _stream()), "fx_to_float")
+    _lib.call("fx_to_float", _ptr(fx), _ptr(out), fx.numel(), int(accumulate), _stream())
 
 
 CAMERA_TYPES = (1, 2, 3)  # CameraType of NS/cameras/cameras.py:42-47: perspective, fisheye, equirectangular
@@ -873,11 +863,11 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
         out["nears"], out["fars"] = f(R, 1), f(R, 1)
         a.nears, a.fars = out["nears"].data_ptr(), out["fars"].data_ptr()
     if cam:
-        _lib.check(_lib.lib().snerf_raygen_cam(C.byref(a), _stream()), "raygen_cam")
+        _lib.call("raygen_cam", C.byref(a), _stream())
     elif lens:
-        _lib.check(_lib.lib().snerf_raygen_lens(C.byref(a), _stream()), "raygen_lens")
+        _lib.call("raygen_lens", C.byref(a), _stream())
     else:
-        _lib.check(_lib.lib().snerf_raygen(C.byref(a), _stream()), "raygen")
+        _lib.call("raygen", C.byref(a), _stream())
     out["camera_indices"] = indices[:, 0:1]
     return out
 
@@ -901,8 +891,7 @@ def pose_apply(c2w: torch.Tensor, pose_adjustment: torch.Tensor, group: Optional
     if group is None and G != M:
         raise RuntimeError(f"pose_apply: {G} pose rows for {M} cameras need a group table")
     out = torch.empty_like(c2w) if out is None else out
-    _lib.check(_lib.lib().snerf_pose_apply(_ptr(c2w), _ptr(pose_adjustment), _ptr(group) if group is not None else None, M, G, _ptr(out), _stream()),
-               "pose_apply")
+    _lib.call("pose_apply", _ptr(c2w), _ptr(pose_adjustment), _ptr(group) if group is not None else None, M, G, _ptr(out), _stream())
     return out
 
 
@@ -943,7 +932,7 @@ def raygen_pose_bwd(indices, fx, fy, cx, cy, c2w, pose_adjustment, g_origins, g_
     a.M, a.G, a.R = M, G, R
     if dyn is not None:  # the pose group's device-side optimiser state (new_adam_dyn): its non-finite flag
         a.nonfinite_flag = dyn.data_ptr()
-    _lib.check(_lib.lib().snerf_raygen_pose_bwd(C.byref(a), _stream()), "raygen_pose_bwd")
+    _lib.call("raygen_pose_bwd", C.byref(a), _stream())
 
 
 def image_time_keys(times: torch.Tensor):
@@ -964,9 +953,9 @@ def sort_rays_by_time(indices: torch.Tensor, image_key: torch.Tensor, n_keys: in
     out = torch.empty_like(indices)
     aux_c = _f32c(aux, "sort_rays_by_time aux").reshape(R, -1) if aux is not None else None
     aux_out = torch.empty_like(aux_c) if aux_c is not None else None
-    _lib.check(_lib.lib().snerf_sort_rays_by_key(_ptr(indices), _ptr(image_key), n_keys, R, _ptr(aux_c) if aux_c is not None else None,
-                                                 aux_c.shape[1] if aux_c is not None else 0, _ptr(out), _ptr(aux_out) if aux_out is not None else None,
-                                                 _stream()), "sort_rays_by_key")
+    _lib.call("sort_rays_by_key", _ptr(indices), _ptr(image_key), n_keys, R, _ptr(aux_c) if aux_c is not None else None,
+              aux_c.shape[1] if aux_c is not None else 0, _ptr(out), _ptr(aux_out) if aux_out is not None else None,
+              _stream())
     return (out, aux_out.view(aux.shape)) if aux is not None else out
 
 
@@ -979,7 +968,7 @@ def ray_time_order(times: torch.Tensor, out: Optional[torch.Tensor] = None) -> t
         out = torch.empty(R, dtype=torch.int32, device=times.device)
     if not out.is_cuda or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < R:
         raise RuntimeError("ray_time_order: out must be a contiguous int32 HIP tensor of at least R elements")
-    _lib.check(_lib.lib().snerf_ray_time_order(_ptr(times), R, _ptr(out), _stream()), "ray_time_order")
+    _lib.call("ray_time_order", _ptr(times), R, _ptr(out), _stream())
     return out[:R]
 
 
@@ -994,8 +983,8 @@ def sample_pixels_uniform(u: torch.Tensor, num_images: int, height: int, width: 
         if not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous() or tuple(images.shape) != (num_images, height, width, 3):
             raise RuntimeError("sample_pixels_uniform: images must be a contiguous uint8 HIP tensor [M,H,W,3]")
         target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
-    _lib.check(_lib.lib().snerf_sample_pixels_uniform(_ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
-                                                      _ptr(target) if target is not None else None, _stream()), "sample_pixels_uniform")
+    _lib.call("sample_pixels_uniform", _ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
+              _ptr(target) if target is not None else None, _stream())
     return idx, target
 
 
@@ -1010,8 +999,8 @@ def sample_pixels_sphere(u: torch.Tensor, num_images: int, height: int, width: i
         if not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous() or tuple(images.shape) != (num_images, height, width, 3):
             raise RuntimeError("sample_pixels_sphere: images must be a contiguous uint8 HIP tensor [M,H,W,3]")
         target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
-    _lib.check(_lib.lib().snerf_sample_pixels_sphere(_ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
-                                                     _ptr(target) if target is not None else None, _stream()), "sample_pixels_sphere")
+    _lib.call("sample_pixels_sphere", _ptr(u), R, num_images, height, width, _ptr(images) if images is not None else None, _ptr(idx),
+              _ptr(target) if target is not None else None, _stream())
     return idx, target
 
 
@@ -1034,8 +1023,7 @@ def mask_pack(mask_bytes: torch.Tensor, n_pixels: int, first_pixel: int, bits: t
     for t, n, what in ((bits, -(-n_pixels // 32), "bits"), (block_counts, -(-n_pixels // MASK_BLOCK), "block_counts")):
         if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
             raise RuntimeError(f"mask_pack: {what} must be a contiguous int32 HIP tensor of at least {n} elements")
-    _lib.check(_lib.lib().snerf_mask_pack(_ptr(mask_bytes), n_pixels, first_pixel, mask_bytes.numel(), _ptr(bits), _ptr(block_counts), _stream()),
-               "mask_pack")
+    _lib.call("mask_pack", _ptr(mask_bytes), n_pixels, first_pixel, mask_bytes.numel(), _ptr(bits), _ptr(block_counts), _stream())
 
 
 class MaskIndex:
@@ -1107,9 +1095,9 @@ def sample_pixels_masked(u: torch.Tensor, index: MaskIndex, num_images: int, hei
         if not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous() or tuple(images.shape) != (num_images, height, width, 3):
             raise RuntimeError("sample_pixels_masked: images must be a contiguous uint8 HIP tensor [M,H,W,3]")
         target = torch.empty(R, 3, dtype=torch.float32, device=u.device)
-    _lib.check(_lib.lib().snerf_sample_pixels_masked(_ptr(u), R, num_images, height, width, _ptr(index.bits), _ptr(index.block_prefix), index.n_blocks,
-                                                     _ptr(images) if images is not None else None, _ptr(idx),
-                                                     _ptr(target) if target is not None else None, _stream()), "sample_pixels_masked")
+    _lib.call("sample_pixels_masked", _ptr(u), R, num_images, height, width, _ptr(index.bits), _ptr(index.block_prefix), index.n_blocks,
+              _ptr(images) if images is not None else None, _ptr(idx),
+              _ptr(target) if target is not None else None, _stream())
     return idx, target
 
 
@@ -1120,6 +1108,6 @@ def aabb_collide(origins, directions, aabb, near_plane: float = 0.0, training: b
     nears = torch.empty(R, 1, dtype=torch.float32, device=origins.device)
     fars = torch.empty_like(nears)
     arr = (C.c_float * 6)(*[v for row in aabb_host(aabb) for v in row])
-    _lib.check(_lib.lib().snerf_aabb_collide(_ptr(origins), _ptr(directions), R, arr, near_plane, int(training), _ptr(nears), _ptr(fars),
-                                             _stream()), "aabb_collide")
+    _lib.call("aabb_collide", _ptr(origins), _ptr(directions), R, arr, near_plane, int(training), _ptr(nears), _ptr(fars),
+              _stream())
     return nears, fars

@@ -32,8 +32,8 @@ def compute_ist(images: torch.Tensor, cam_ids: torch.Tensor, cam_times: torch.Te
     M, H, W = images.shape[:3]
     off, idx = temporal_neighbours(cam_ids.to(images.device), cam_times.to(images.device), ist_range)
     out = torch.empty(M, H, W, dtype=torch.float16, device=images.device)
-    _lib.check(_lib.lib().snerf_ist_maps(ops._ptr(images), 0 if images.dtype == torch.uint8 else 1, M, H, W, ops._ptr(off), ops._ptr(idx), alpha,
-                                         ops._ptr(out), ops._stream()), "ist_maps")
+    _lib.call("ist_maps", ops._ptr(images), 0 if images.dtype == torch.uint8 else 1, M, H, W, ops._ptr(off), ops._ptr(idx), alpha,
+              ops._ptr(out), ops._stream())
     return out
 
 
@@ -55,9 +55,8 @@ def compute_isg(images: torch.Tensor, cam_ids: torch.Tensor, isg_gamma: float = 
     med = torch.empty(uniq.numel(), H, W, 3, dtype=images.dtype, device=dev)
     out = torch.empty(M, H, W, dtype=torch.float16, device=dev)
     cam_img, img_cam = order.to(torch.int32).contiguous(), inv.to(torch.int32).contiguous()  # named: they must outlive the launch
-    _lib.check(_lib.lib().snerf_isg_maps(ops._ptr(images), 0 if images.dtype == torch.uint8 else 1, M, H, W, uniq.numel(), ops._ptr(off),
-                                         ops._ptr(cam_img), ops._ptr(img_cam), max_frames, isg_gamma, ops._ptr(med), ops._ptr(out), ops._stream()),
-               "isg_maps")
+    _lib.call("isg_maps", ops._ptr(images), 0 if images.dtype == torch.uint8 else 1, M, H, W, uniq.numel(), ops._ptr(off),
+              ops._ptr(cam_img), ops._ptr(img_cam), max_frames, isg_gamma, ops._ptr(med), ops._ptr(out), ops._stream())
     return out
 
 
@@ -261,8 +260,8 @@ class DynamicBasedPixelSampler(PixelSampler):
             chosen = nonempty[torch.randperm(nonempty.numel(), device=device)[:k]].contiguous()  # random.shuffle + skip empty maps (:376-399)
             u = torch.rand(n, device=device)
             idx = torch.empty(n, 3, dtype=torch.int64, device=device)
-            _lib.check(_lib.lib().snerf_ist_sample(ops._ptr(batch["ist_cdf"]), image_height, image_width, ops._ptr(chosen), ops._ptr(batch["ist_nnz"]),
-                                                   per_image, ops._ptr(u), n, ops._ptr(idx), ops._stream()), "ist_sample")
+            _lib.call("ist_sample", ops._ptr(batch["ist_cdf"]), image_height, image_width, ops._ptr(chosen), ops._ptr(batch["ist_nnz"]),
+                      per_image, ops._ptr(u), n, ops._ptr(idx), ops._stream())
             parts.append(idx)
         parts.append(super().sample_method(batch_size - n, num_images, image_height, image_width, mask=mask, batch=batch, device=device))
         return torch.cat(parts, dim=0)

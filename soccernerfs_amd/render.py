@@ -47,6 +47,7 @@ class KPlanesRenderer:
     _FIELD_SLICE = 4096  # rays per launch group of the unfused (fp32-operand) field: bounds the [N, 32 n_scales] feature buffer
 
     # the launches whose argument lists the fused trainers share (fused_step.py), on this object's buffers
+    _call = FusedStep._call  # through this object's _ck, which counts the launches
     _p = FusedStep._p
     _span = FusedStep._span
     _spaced_bins = FusedStep._spaced_bins
@@ -116,16 +117,16 @@ class KPlanesRenderer:
 
     # ---- one chunk ----
     def _chunk(self, ra, p0: int, p1: int, anneal: float, out: Dict[str, torch.Tensor]):
-        tr, b, rays, lib = self.trainer, self.buf, self._rays, self.lib
+        tr, b, rays = self.trainer, self.buf, self._rays
         n = p1 - p0
         ra.p0, ra.p1 = p0, p1
         with self._span("raygen_frame"):
             if isinstance(ra, _lib.RaygenFrameCamArgs):
-                self._ck(lib.snerf_raygen_frame_cam(C.byref(ra), self._st), "raygen_frame_cam")
+                self._call("raygen_frame_cam", C.byref(ra), self._st)
             elif isinstance(ra, _lib.RaygenFrameLensArgs):
-                self._ck(lib.snerf_raygen_frame_lens(C.byref(ra), self._st), "raygen_frame_lens")
+                self._call("raygen_frame_lens", C.byref(ra), self._st)
             else:
-                self._ck(lib.snerf_raygen_frame(C.byref(ra), self._st), "raygen_frame")
+                self._call("raygen_frame", C.byref(ra), self._st)
         self.rays, self._fwd_rays = rays, n
         self._spaced_bins(None)
         o, d, t = rays["origins"], rays["directions"], rays["times"]
@@ -134,12 +135,12 @@ class KPlanesRenderer:
             N, net = n * self.S[lvl], tr.prop_nets[lvl]
             if tr.fused_proposal:
                 with self._span("kplanes_density_fwd"):
-                    self._ck(lib.snerf_kplanes_density_fwd(C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
-                                                           C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]), None, self._st), "kplanes_density_fwd")
+                    self._call("kplanes_density_fwd", C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), N,
+                               C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]), None, self._st)
             else:
                 with self._span("kplanes_gather_fwd.prop"):
-                    self._ck(lib.snerf_kplanes_gather_fwd(C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
-                                                          self._p(b["pfeat"][lvl]), self._st), "gather_fwd")
+                    self._call("kplanes_gather_fwd", C.byref(tr._desc_prop[lvl]), self._p(tr.prop_planes[lvl].planes), C.byref(co), N,
+                               self._p(b["pfeat"][lvl]), self._st)
                 self._mlp_fwd(net, b["pfeat"][lvl], self.cfg.proposal_feature_dim, N, b["pout"][lvl], 1, 0, b["dens"][lvl])
             self._resample(lvl, None, anneal)
         S2 = self.S[2]
@@ -148,17 +149,16 @@ class KPlanesRenderer:
         if self.fused_tail:
             sd = self.samples_done[p0:p1] if self.samples_done is not None else None
             with self._span("kplanes_field_render"):
-                self._ck(lib.snerf_kplanes_field_render(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), n, C.byref(tr.sigma_net.desc),
-                                                        self._p(tr.sigma_net.params), C.byref(tr.color_net.desc), self._p(tr.color_net.params),
-                                                        self.transmittance_cutoff, self._p(rgb), self._p(acc), self._p(depth), None, None,
-                                                        self._p(sd) if sd is not None else None, self._st), "kplanes_field_render")
+                self._call("kplanes_field_render", C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), n, C.byref(tr.sigma_net.desc),
+                           self._p(tr.sigma_net.params), C.byref(tr.color_net.desc), self._p(tr.color_net.params),
+                           self.transmittance_cutoff, self._p(rgb), self._p(acc), self._p(depth), None, None,
+                           self._p(sd) if sd is not None else None, self._st)
             return
         if tr.fused_field:
             with self._span("kplanes_field_fwd"):
-                self._ck(lib.snerf_kplanes_field_fwd(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), C.c_int64(n * S2),
-                                                     C.byref(tr.sigma_net.desc), self._p(tr.sigma_net.params), C.byref(tr.color_net.desc),
-                                                     self._p(tr.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]), None, None, None, self._st),
-                         "kplanes_field_fwd")
+                self._call("kplanes_field_fwd", C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(co), n * S2,
+                           C.byref(tr.sigma_net.desc), self._p(tr.sigma_net.params), C.byref(tr.color_net.desc),
+                           self._p(tr.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]), None, None, None, self._st)
         else:  # exact-fp32 operands (or fused_field off): gather + the generic MLP kernels, as the trainer's forward, a slice of rays at a time
             F = tr.field_planes.out_dim
             for r0 in range(0, n, self._FIELD_SLICE):
@@ -166,18 +166,18 @@ class KPlanesRenderer:
                 N = (r1 - r0) * S2
                 cs = ops.coords_from_rays(o[r0:r1], d[r0:r1], t[r0:r1], b["eb"][2][r0:r1], self.aabb, True)
                 with self._span("kplanes_gather_fwd.field"):
-                    self._ck(lib.snerf_kplanes_gather_fwd(C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(cs), C.c_int64(N), self._p(b["feat"]),
-                                                          self._st), "gather_fwd")
+                    self._call("kplanes_gather_fwd", C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(cs), N, self._p(b["feat"]),
+                               self._st)
                 self._mlp_fwd(tr.sigma_net, b["feat"], F, N, b["h"], 16, 15, b["dens"][2][r0:r1])
                 rgb_s = b["rgb"][r0 * S2:r1 * S2]
                 if tr.view_dependent:
                     with self._span("kplanes_color_input_fwd"):
-                        self._ck(lib.snerf_kplanes_color_input_fwd(self._p(d[r0:r1]), S2, self._p(b["h"]), C.c_int64(N), self._p(b["cx"]), self._st), "color_input_fwd")
+                        self._call("kplanes_color_input_fwd", self._p(d[r0:r1]), S2, self._p(b["h"]), N, self._p(b["cx"]), self._st)
                     self._mlp_fwd(tr.color_net, b["cx"], 32, N, rgb_s, 3)
                 else:
                     self._mlp_fwd(tr.color_net, b["h"], 16, N, rgb_s, 3)
         with self._span("weights_render_fwd"):
-            self._ck(lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), n, S2, self._p(b["w"][2]), self._st), "weights_fwd")
+            self._call("weights_fwd", self._p(b["dens"][2]), self._p(b["eb"][2]), n, S2, self._p(b["w"][2]), self._st)
             b["rgb_out"], b["acc"], b["depth"] = rgb, acc, depth
             self._render_fwd(False, 1, None, "depth_median")
 

@@ -141,8 +141,7 @@ class TiledHashTableBackward:
 
         self.enc, self.B = enc, int(B)
         self.plan = _lib.HashgridTilePlan()
-        _lib.check(_lib.lib().snerf_hashgrid_tile_plan_make(C.byref(enc.desc), C.c_int64(B), tile_rows_log2, first_tiled_level, C.byref(self.plan)),
-                   "hashgrid_tile_plan_make")
+        _lib.call("hashgrid_tile_plan_make", C.byref(enc.desc), B, tile_rows_log2, first_tiled_level, C.byref(self.plan))
         dev = enc.params.device
         self.counts = torch.empty(max(int(self.plan.count_ints), 1), dtype=torch.int32, device=dev)
         self.tile_base = torch.empty(self.plan.n_tiles + 1, dtype=torch.int32, device=dev)
@@ -153,9 +152,9 @@ class TiledHashTableBackward:
         import ctypes as C
 
         st = stream if stream is not None else ops._stream()
-        _lib.check(_lib.lib().snerf_hashgrid_bwd_bin(C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), C.c_int64(self.B),
-                                                     ops._ptr(gout) if gout is not None else None, ops._ptr(self.counts),
-                                                     ops._ptr(self.tile_base), ops._ptr(self.records), st), "hashgrid_bwd_bin")
+        _lib.call("hashgrid_bwd_bin", C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), self.B,
+                  ops._ptr(gout) if gout is not None else None, ops._ptr(self.counts),
+                  ops._ptr(self.tile_base), ops._ptr(self.records), st)
 
     def coarse_levels(self, x: torch.Tensor, gout: torch.Tensor, gtable: torch.Tensor, stream=None):
         import ctypes as C
@@ -163,22 +162,22 @@ class TiledHashTableBackward:
         lc = self.plan.first_tiled_level
         if lc > 0:
             st = stream if stream is not None else ops._stream()
-            _lib.check(_lib.lib().snerf_hashgrid_encode_bwd_levels(C.byref(self.enc.desc), None, ops._ptr(x), C.c_int64(self.B), ops._ptr(gout), ops._ptr(gtable), None, 0, lc,
-                                                                   st), "hashgrid_encode_bwd_levels")
+            _lib.call("hashgrid_encode_bwd_levels", C.byref(self.enc.desc), None, ops._ptr(x), self.B, ops._ptr(gout), ops._ptr(gtable), None, 0, lc,
+                      st)
 
     def scatter(self, x: torch.Tensor, gout: torch.Tensor, gtable: torch.Tensor, stream=None):
         """gtable += the tiled levels' share (after `bin`; `coarse_levels` adds the rest)."""
         import ctypes as C
 
         st = stream if stream is not None else ops._stream()
-        _lib.check(_lib.lib().snerf_hashgrid_bwd_tiles(C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), C.c_int64(self.B), ops._ptr(gout), ops._ptr(self.tile_base),
-                                                       ops._ptr(self.records), ops._ptr(gtable), st), "hashgrid_bwd_tiles")
+        _lib.call("hashgrid_bwd_tiles", C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), self.B, ops._ptr(gout), ops._ptr(self.tile_base),
+                  ops._ptr(self.records), ops._ptr(gtable), st)
 
     def scatter_adam(self, x: torch.Tensor, gout: torch.Tensor, gtable: Optional[torch.Tensor], p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, step: int,
                      eps: float, betas=(0.9, 0.999), stream=None):
         import ctypes as C
 
         st = stream if stream is not None else ops._stream()
-        _lib.check(_lib.lib().snerf_hashgrid_bwd_tiles_adam(C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), C.c_int64(self.B), ops._ptr(gout),
-                                                            ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable) if gtable is not None else None, ops._ptr(p),
-                                                            ops._ptr(m), ops._ptr(v), lr, betas[0], betas[1], eps, step, st), "hashgrid_bwd_tiles_adam")
+        _lib.call("hashgrid_bwd_tiles_adam", C.byref(self.enc.desc), C.byref(self.plan), ops._ptr(x), self.B, ops._ptr(gout),
+                  ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable) if gtable is not None else None, ops._ptr(p),
+                  ops._ptr(m), ops._ptr(v), lr, betas[0], betas[1], eps, step, st)

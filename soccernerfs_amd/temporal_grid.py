@@ -43,20 +43,20 @@ class _Encode(torch.autograd.Function):
         if xyz is not None and xyz.requires_grad:
             # calc_grad_inputs (temporal_grid.py:82-87): d out / d xyz is kept for the backward, [B, L, D, C]
             ctx.dy_dx = torch.empty(B, enc.num_levels, enc.input_dim, enc.level_dim, dtype=torch.float32, device=embeddings.device)
-            _lib.check(_lib.lib().snerf_tgrid_encode_fwd_dydx(C.byref(enc.desc), ops._ptr(embeddings), C.byref(coords),
-                                                              ops._ptr(trow) if trow is not None else None, ops._ptr(times) if times is not None else None,
-                                                              spr, C.c_int64(B), ops._ptr(out), ops._ptr(ctx.dy_dx), ops._stream()), "tgrid_encode_fwd_dydx")
+            _lib.call("tgrid_encode_fwd_dydx", C.byref(enc.desc), ops._ptr(embeddings), C.byref(coords),
+                      ops._ptr(trow) if trow is not None else None, ops._ptr(times) if times is not None else None,
+                      spr, B, ops._ptr(out), ops._ptr(ctx.dy_dx), ops._stream())
         else:
-            _lib.check(_lib.lib().snerf_tgrid_encode_fwd(C.byref(enc.desc), ops._ptr(embeddings), C.byref(coords),
-                                                         ops._ptr(trow) if trow is not None else None, ops._ptr(times) if times is not None else None,
-                                                         spr, C.c_int64(B), ops._ptr(out), ops._stream()), "tgrid_encode_fwd")
+            _lib.call("tgrid_encode_fwd", C.byref(enc.desc), ops._ptr(embeddings), C.byref(coords),
+                      ops._ptr(trow) if trow is not None else None, ops._ptr(times) if times is not None else None,
+                      spr, B, ops._ptr(out), ops._stream())
         ctx.enc, ctx.coords, ctx.keep, ctx.trow, ctx.times, ctx.spr, ctx.B = enc, coords, coords_keep, trow, times, spr, B
         ctx.shape, ctx.tv = embeddings.shape, None
         if tv_a is None:
             return out, None
         part = torch.zeros(64, 16, dtype=torch.float32, device=embeddings.device)
-        _lib.check(_lib.lib().snerf_tgrid_tv_fwd(ops._ptr(embeddings), C.c_int64(embeddings.shape[0]), embeddings.shape[1], tv_a, tv_b, ops._ptr(part), 64,
-                                                 ops._stream()), "tgrid_tv_fwd")
+        _lib.call("tgrid_tv_fwd", ops._ptr(embeddings), embeddings.shape[0], embeddings.shape[1], tv_a, tv_b, ops._ptr(part), 64,
+                  ops._stream())
         ctx.tv = (tv_a, tv_b)
         ctx.save_for_backward(embeddings)
         return out, part[:, 0].sum() / embeddings.shape[0]
@@ -71,16 +71,16 @@ class _Encode(torch.autograd.Function):
             g = g.contiguous()
             if ctx.dy_dx is not None:  # kernel_input_backward (temporal_gridencoder.cu:373-398)
                 gxyz = torch.empty(ctx.B, enc.input_dim, dtype=torch.float32, device=g.device)
-                _lib.check(_lib.lib().snerf_tgrid_input_bwd(ops._ptr(g), ops._ptr(ctx.dy_dx), C.c_int64(ctx.B), enc.input_dim, enc.level_dim, enc.num_levels,
-                                                            ops._ptr(gxyz), ops._stream()), "tgrid_input_bwd")
-            _lib.check(_lib.lib().snerf_tgrid_encode_bwd(C.byref(enc.desc), C.byref(ctx.coords), ops._ptr(ctx.trow) if ctx.trow is not None else None,
-                                                         ops._ptr(ctx.times) if ctx.times is not None else None, ctx.spr, C.c_int64(ctx.B), ops._ptr(g),
-                                                         ops._ptr(gemb), ops._stream()), "tgrid_encode_bwd")
+                _lib.call("tgrid_input_bwd", ops._ptr(g), ops._ptr(ctx.dy_dx), ctx.B, enc.input_dim, enc.level_dim, enc.num_levels,
+                          ops._ptr(gxyz), ops._stream())
+            _lib.call("tgrid_encode_bwd", C.byref(enc.desc), C.byref(ctx.coords), ops._ptr(ctx.trow) if ctx.trow is not None else None,
+                      ops._ptr(ctx.times) if ctx.times is not None else None, ctx.spr, ctx.B, ops._ptr(g),
+                      ops._ptr(gemb), ops._stream())
         if g_tv is not None and ctx.tv is not None:
             (emb,) = ctx.saved_tensors
             gt = g_tv.detach().reshape(1).float().contiguous()
-            _lib.check(_lib.lib().snerf_tgrid_tv_bwd(ops._ptr(emb), C.c_int64(ctx.shape[0]), ctx.shape[1], ctx.tv[0], ctx.tv[1], ops._ptr(gt), ops._ptr(gemb),
-                                                     ops._stream()), "tgrid_tv_bwd")
+            _lib.call("tgrid_tv_bwd", ops._ptr(emb), ctx.shape[0], ctx.shape[1], ctx.tv[0], ctx.tv[1], ops._ptr(gt), ops._ptr(gemb),
+                      ops._stream())
         # accumulate_into_grad (set by optimizers.FusedAdam): the scatter went straight into the persistent, optimiser-cleared
         # .grad buffer; returning None keeps autograd from allocating / adding a second dense tensor
         return (None if acc is not None else gemb), None, None, None, None, None, None, None, None, None, gxyz
@@ -195,7 +195,7 @@ class TiledTableBackward:
     def __init__(self, enc: "TemporalGridEncoder", B: int, tile_rows_log2: int = 0, first_tiled_level: int = -1):
         self.enc, self.B = enc, int(B)
         self.plan = _lib.TgridTilePlan()
-        _lib.check(_lib.lib().snerf_tgrid_tile_plan_make(C.byref(enc.desc), C.c_int64(B), tile_rows_log2, first_tiled_level, C.byref(self.plan)), "tile_plan_make")
+        _lib.call("tgrid_tile_plan_make", C.byref(enc.desc), B, tile_rows_log2, first_tiled_level, C.byref(self.plan))
         dev = enc.embeddings.device
         self.counts = torch.empty(max(int(self.plan.count_ints), 1), dtype=torch.int32, device=dev)
         self.tile_base = torch.zeros(self.plan.n_tiles + 1, dtype=torch.int32, device=dev)
@@ -214,22 +214,22 @@ class TiledTableBackward:
     def bin(self, coords: _lib.Coords, times: torch.Tensor, spr: int, gout: Optional[torch.Tensor], stream=None):
         """gout = None: file every in-range sample (the pass then needs the sample positions only and can run beside the forward)."""
         st = stream if stream is not None else ops._stream()
-        _lib.check(_lib.lib().snerf_tgrid_bwd_bin(C.byref(self.enc.desc), C.byref(self.plan), C.byref(coords), ops._ptr(times), spr, C.c_int64(self.B),
-                                                  ops._ptr(gout) if gout is not None else None, ops._ptr(self.pos4), ops._ptr(self.counts), ops._ptr(self.tile_base), ops._ptr(self.records), st), "tgrid_bwd_bin")
+        _lib.call("tgrid_bwd_bin", C.byref(self.enc.desc), C.byref(self.plan), C.byref(coords), ops._ptr(times), spr, self.B,
+                  ops._ptr(gout) if gout is not None else None, ops._ptr(self.pos4), ops._ptr(self.counts), ops._ptr(self.tile_base), ops._ptr(self.records), st)
 
     def coarse_levels(self, coords: _lib.Coords, times: torch.Tensor, spr: int, gout: torch.Tensor, gtable: torch.Tensor, stream=None):
         """Levels [0, first_tiled_level) through the run-length atomic kernel into gtable; reads the ray buffers, so it belongs on their stream."""
         lc = self.plan.first_tiled_level
         if lc > 0:
             st = stream if stream is not None else ops._stream()
-            _lib.check(_lib.lib().snerf_tgrid_encode_bwd_levels(C.byref(self.enc.desc), C.byref(coords), None, ops._ptr(times), spr, C.c_int64(self.B), ops._ptr(gout),
-                                                                ops._ptr(gtable), 0, lc, st), "tgrid_encode_bwd_levels")
+            _lib.call("tgrid_encode_bwd_levels", C.byref(self.enc.desc), C.byref(coords), None, ops._ptr(times), spr, self.B, ops._ptr(gout),
+                      ops._ptr(gtable), 0, lc, st)
 
     def scatter(self, gout: torch.Tensor, gtable: torch.Tensor, stream=None):
         """gtable += the tiled levels' share of d loss / d table (after `bin` of the same batch; `coarse_levels` adds the rest)."""
         st = stream if stream is not None else ops._stream()
-        _lib.check(_lib.lib().snerf_tgrid_bwd_tiles(C.byref(self.enc.desc), C.byref(self.plan), C.c_int64(self.B), ops._ptr(gout), ops._ptr(self.pos4),
-                                                    ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable), st), "tgrid_bwd_tiles")
+        _lib.call("tgrid_bwd_tiles", C.byref(self.enc.desc), C.byref(self.plan), self.B, ops._ptr(gout), ops._ptr(self.pos4),
+                  ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable), st)
 
     def scatter_adam(self, gout: torch.Tensor, gtable: Optional[torch.Tensor], p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, eps: float,
                      tv_cols=None, srow: Optional[torch.Tensor] = None, betas=(0.9, 0.999), stream=None):
@@ -237,7 +237,7 @@ class TiledTableBackward:
         `coarse_levels` of the same batch."""
         st = stream if stream is not None else ops._stream()
         ca, cb = tv_cols if tv_cols is not None else (-1, -1)
-        _lib.check(_lib.lib().snerf_tgrid_bwd_tiles_adam(C.byref(self.enc.desc), C.byref(self.plan), C.c_int64(self.B), ops._ptr(gout), ops._ptr(self.pos4),
-                                                         ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable) if gtable is not None else None,
-                                                         ops._ptr(p), ops._ptr(m), ops._ptr(v), lr, betas[0], betas[1], eps, step, ca, cb,
-                                                         ops._ptr(srow) if srow is not None else None, st), "tgrid_bwd_tiles_adam")
+        _lib.call("tgrid_bwd_tiles_adam", C.byref(self.enc.desc), C.byref(self.plan), self.B, ops._ptr(gout), ops._ptr(self.pos4),
+                  ops._ptr(self.tile_base), ops._ptr(self.records), ops._ptr(gtable) if gtable is not None else None,
+                  ops._ptr(p), ops._ptr(m), ops._ptr(v), lr, betas[0], betas[1], eps, step, ca, cb,
+                  ops._ptr(srow) if srow is not None else None, st)

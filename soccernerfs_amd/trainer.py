@@ -432,16 +432,16 @@ class KPlanesTrainer(FusedStep):
 
     def _gather(self, desc, planes, coords, N, out):
       with self._span("kplanes_gather_fwd.field" if desc is self._desc_field else "kplanes_gather_fwd.prop"):
-        _lib.check(self.lib.snerf_kplanes_gather_fwd(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(out), self._st), "gather_fwd")
+        self._call("kplanes_gather_fwd", C.byref(desc), self._p(planes), C.byref(coords), N, self._p(out), self._st)
 
     def _scatter(self, desc, planes, coords, N, gout, gplanes):
       with self._span("kplanes_gather_bwd.field" if desc is self._desc_field else "kplanes_gather_bwd.prop"):
         if self.grads_fx is not None:
-            _lib.check(self.lib.snerf_kplanes_gather_bwd_fx(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gout),
-                                                            self._p(self.fx(gplanes)), self._st), "gather_bwd_fx")
+            self._call("kplanes_gather_bwd_fx", C.byref(desc), self._p(planes), C.byref(coords), N, self._p(gout),
+                       self._p(self.fx(gplanes)), self._st)
         else:
-            _lib.check(self.lib.snerf_kplanes_gather_bwd(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gout), self._p(gplanes),
-                                                         self._st), "gather_bwd")
+            self._call("kplanes_gather_bwd", C.byref(desc), self._p(planes), C.byref(coords), N, self._p(gout), self._p(gplanes),
+                       self._st)
 
     def _mlp_bwd(self, net, gname, X, ldx, N, gY, ldgy, aux_col, gaux, gX, ldgx, x16=False):
         """FusedStep._mlp_bwd for the net whose gradient segment is `gname`, through its weight-gradient workspace where it has one;
@@ -453,15 +453,15 @@ class KPlanesTrainer(FusedStep):
         with self._span(f"mlp_bwd.{net.desc.d_in}x{net.desc.hidden}x{net.desc.n_hidden}"):
             if ws is not None:
                 self._ws_dirty.add(gname)
-            fn, what = (self.lib.snerf_mlp_bwd_ws, "mlp_bwd_ws") if ws is not None else (self.lib.snerf_mlp_bwd_x16, "mlp_bwd")
-            _lib.check(fn(C.byref(net.desc), self._p(net.params), self._p(X), ldx, C.c_int64(N), self._p(gY) if gY is not None else None, ldgy, aux_col,
-                          self._p(gaux) if gaux is not None else None, self._p(gX) if gX is not None else None, ldgx,
-                          self._p(ws if ws is not None else self.gviews[gname]), self._st), what)
+            self._call("mlp_bwd_ws" if ws is not None else "mlp_bwd_x16",
+                       C.byref(net.desc), self._p(net.params), self._p(X), ldx, N, self._p(gY) if gY is not None else None, ldgy, aux_col,
+                       self._p(gaux) if gaux is not None else None, self._p(gX) if gX is not None else None, ldgx,
+                       self._p(ws if ws is not None else self.gviews[gname]), self._st)
 
     def _color_input(self, dirs, N, h, cx):
         """cx[:N] = [SH4 of the ray directions | h[:, :15] | 0] (view-dependent colour net, generic MLP kernels)."""
         with self._span("kplanes_color_input_fwd"):
-            _lib.check(self.lib.snerf_kplanes_color_input_fwd(self._p(dirs), self.S[2], self._p(h), C.c_int64(N), self._p(cx), self._st), "color_input_fwd")
+            self._call("kplanes_color_input_fwd", self._p(dirs), self.S[2], self._p(h), N, self._p(cx), self._st)
 
     def _color_backward(self, r0: int, r1: int):
         """Colour-net backward for rays [r0, r1): d loss / d weights -> field.color, d loss / d h[:, :15] -> gh[:, :15] (gh[:, 15] stays 0: the density
@@ -479,17 +479,16 @@ class KPlanesTrainer(FusedStep):
             with self._span("color_bwd_vd"):
                 if ws is not None:
                     self._ws_dirty.add("field.color")
-                    _lib.check(self.lib.snerf_kplanes_color_bwd_vd_ws(C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), C.c_int64(N),
-                                                                      self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(ws), self._st), "color_bwd_vd_ws")
+                    self._call("kplanes_color_bwd_vd_ws", C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), N,
+                               self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(ws), self._st)
                 else:
-                    _lib.check(self.lib.snerf_kplanes_color_bwd_vd(C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), C.c_int64(N),
-                                                                   self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(self.gviews["field.color"]), self._st),
-                               "color_bwd_vd")
+                    self._call("kplanes_color_bwd_vd", C.byref(net.desc), self._p(net.params), self._p(dirs), S2, self._p(sl(b["h"])), N,
+                               self._p(sl(b["grgb"])), 3, self._p(sl(b["gh"])), self._p(self.gviews["field.color"]), self._st)
             return
         self._color_input(dirs, N, sl(b["h"]), sl(b["cx"]))
         self._mlp_bwd(self.color_net, "field.color", sl(b["cx"]), 32, N, sl(b["grgb"]), 3, -1, None, sl(b["gcx"]), 32)
         with self._span("kplanes_color_input_bwd"):
-            _lib.check(self.lib.snerf_kplanes_color_input_bwd(self._p(sl(b["gcx"])), 32, C.c_int64(N), self._p(sl(b["gh"])), self._st), "color_input_bwd")
+            self._call("kplanes_color_input_bwd", self._p(sl(b["gcx"])), 32, N, self._p(sl(b["gh"])), self._st)
 
     def _reduce_mlp_grads(self, names):
         """Folds the weight-gradient workspaces of `names` into self.grads (current stream) and clears them; only those a backward kernel of this
@@ -498,7 +497,7 @@ class KPlanesTrainer(FusedStep):
             if gname in self._ws_dirty:
                 net = self._mlp_nets[gname]
                 with self._span("mlp_gw_reduce"):
-                    _lib.check(self.lib.snerf_mlp_gw_reduce(C.byref(net.desc), self._p(self._mlp_ws[gname]), self._p(self.gviews[gname]), self._st), "mlp_gw_reduce")
+                    self._call("mlp_gw_reduce", C.byref(net.desc), self._p(self._mlp_ws[gname]), self._p(self.gviews[gname]), self._st)
                 self._ws_dirty.discard(gname)
 
     # -------------------------------------------------------------------------------------------
@@ -531,7 +530,7 @@ class KPlanesTrainer(FusedStep):
         o, d, t = rays["origins"], rays["directions"], rays["times"].reshape(-1) if rays["times"] is not None else None
         if self.field_fwd_time_order:  # first on the main stream: done long before the field forward, under the previous step's sweep
             with self._span("ray_time_order"):
-                _lib.check(self.lib.snerf_ray_time_order(self._p(t), R, self._p(self._ray_order), self._st), "ray_time_order")
+                self._call("ray_time_order", self._p(t), R, self._p(self._ray_order), self._st)
         if "nears" not in rays:
             rays["nears"], rays["fars"] = ops.aabb_collide(o, d, self.aabb, cfg.near_plane, training)
         else:
@@ -547,11 +546,10 @@ class KPlanesTrainer(FusedStep):
             if lvl < 2 and self.fused_proposal:
                 net = self.prop_nets[lvl]
                 with self._span("kplanes_density_fwd"):
-                    _lib.check(self.lib.snerf_kplanes_density_fwd(C.byref(self._desc_prop[lvl]), self._p(self.prop_planes[lvl].planes), C.byref(co), C.c_int64(N),
-                                                                  C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]),
-                                                                  self._p(b["pfeat"][lvl]) if training and self._keep_pfeat and not self.fused_proposal_backward
-                                                                  else None, self._st),
-                               "kplanes_density_fwd")
+                    self._call("kplanes_density_fwd", C.byref(self._desc_prop[lvl]), self._p(self.prop_planes[lvl].planes), C.byref(co), N,
+                               C.byref(net.desc), self._p(net.params), self._p(b["dens"][lvl]),
+                               self._p(b["pfeat"][lvl]) if training and self._keep_pfeat and not self.fused_proposal_backward
+                               else None, self._st)
                 self._resample(lvl, rng["u"][lvl] if training else None, anneal)
             elif lvl < 2:
                 self._gather(self._desc_prop[lvl], self.prop_planes[lvl].planes, co, N, b["pfeat"][lvl])
@@ -571,13 +569,13 @@ class KPlanesTrainer(FusedStep):
                 self._qg_step = bool(self._fwd_fused and self.quotient_epilogue and will_sort)
                 if self._fwd_fused:
                     with self._span("kplanes_field_fwd"):
-                        _lib.check(self.lib.snerf_kplanes_field_fwd_ordered(
-                            C.byref(self._desc_field), self._p(self.field_planes.planes), C.byref(co), C.c_int64(N),
+                        self._call(
+                            "kplanes_field_fwd_ordered", C.byref(self._desc_field), self._p(self.field_planes.planes), C.byref(co), N,
                             C.byref(self.sigma_net.desc), self._p(self.sigma_net.params), C.byref(self.color_net.desc),
                             self._p(self.color_net.params), self._p(b["dens"][2]), self._p(b["rgb"]),
                             self._p(b["feat16"]) if keep else None, self._p(b["h"]) if keep else None,
                             self._p(b["feat"]) if keep and self.quotient_scatter and not self._qg_step else None,
-                            self._p(self._ray_order) if self.field_fwd_time_order else None, self._st), "kplanes_field_fwd")
+                            self._p(self._ray_order) if self.field_fwd_time_order else None, self._st)
                 else:
                     self._gather(self._desc_field, self.field_planes.planes, co, N, b["feat"])
                 if will_sort and not sort_early:
@@ -592,7 +590,7 @@ class KPlanesTrainer(FusedStep):
                         self._mlp_fwd(self.color_net, b["h"], 16, N, b["rgb"], 3)
                 self._render_deferred = bool(training and defer_render)
                 if not self._render_deferred:
-                    _lib.check(self.lib.snerf_weights_fwd(self._p(b["dens"][2]), self._p(b["eb"][2]), R, self.S[2], self._p(b["w"][2]), self._st), "weights_fwd")
+                    self._call("weights_fwd", self._p(b["dens"][2]), self._p(b["eb"][2]), R, self.S[2], self._p(b["w"][2]), self._st)
         if self._render_deferred:
             return b["rgb_out"][:R]
         if training:
@@ -629,17 +627,17 @@ class KPlanesTrainer(FusedStep):
         b, co = self.buf, self.cfg.loss_coefficients
         b["reg"].zero_()
         with self._span("plane_reg.all"):
-            _lib.check(self.lib.snerf_plane_reg(C.byref(self._desc_field), self._p(self.field_planes.planes), self._p(self.gviews["field.planes"]),
-                                                co["space_tv_loss"], co["time_smoothness_loss"], co["sparse_transients_loss"], self._p(b["reg"][0]),
-                                                ops.REG_SLOTS, 1, self._st), "plane_reg")
+            self._call("plane_reg", C.byref(self._desc_field), self._p(self.field_planes.planes), self._p(self.gviews["field.planes"]),
+                       co["space_tv_loss"], co["time_smoothness_loss"], co["sparse_transients_loss"], self._p(b["reg"][0]),
+                       ops.REG_SLOTS, 1, self._st)
             for lvl in range(2):
-                _lib.check(self.lib.snerf_plane_reg(C.byref(self._desc_prop[lvl]), self._p(self.prop_planes[lvl].planes),
-                                                    self._p(self.gviews[f"prop{lvl}.planes"]), co["space_tv_proposal_loss"],
-                                                    co["time_smoothness_proposal_loss"], co["sparse_transients_proposal_loss"],
-                                                    self._p(b["reg"][1 + lvl]), ops.REG_SLOTS, 1, self._st), "plane_reg")
+                self._call("plane_reg", C.byref(self._desc_prop[lvl]), self._p(self.prop_planes[lvl].planes),
+                           self._p(self.gviews[f"prop{lvl}.planes"]), co["space_tv_proposal_loss"],
+                           co["time_smoothness_proposal_loss"], co["sparse_transients_proposal_loss"],
+                           self._p(b["reg"][1 + lvl]), ops.REG_SLOTS, 1, self._st)
 
     def lib_quotient_ok(self, N: int) -> bool:
-        return bool(_lib.lib().snerf_kplanes_quotient_supported(C.byref(self._desc_field), C.c_int64(N)))
+        return bool(_lib.lib().snerf_kplanes_quotient_supported(C.byref(self._desc_field), N))
 
     def _scatter_field_scales(self, co, lo: int, hi: int, fixup: bool = True):
         """Pass B of the field's sorted scatter for scales [lo, hi): product form (gradient vectors from gradvec / the fused backward) or
@@ -651,8 +649,8 @@ class KPlanesTrainer(FusedStep):
                     ss.quotient_fixup_scales(self.field_planes.planes, co, self.gviews["field.planes"], lo, hi, self._st)
                 ss.quotient_pass_b_scales(self.field_planes.planes, self.gviews["field.planes"], lo, hi, self._st)
             else:
-                _lib.check(self.lib.snerf_kplanes_scatter_sorted_scales(C.byref(ss.desc), C.c_int64(ss.N), self._p(ss.gvec), ss.gvec_bf16, self._p(ss.sorted_rec),
-                                                                        self._p(self.gviews["field.planes"]), lo, hi, self._st), "scatter_sorted")
+                self._call("kplanes_scatter_sorted_scales", C.byref(ss.desc), ss.N, self._p(ss.gvec), ss.gvec_bf16, self._p(ss.sorted_rec),
+                           self._p(self.gviews["field.planes"]), lo, hi, self._st)
 
     def _field_backward_chunk(self, r0: int, r1: int):
         """colour-net bwd -> sigma-net bwd -> plane scatter for rays [r0, r1) of the nerf level."""
@@ -668,11 +666,11 @@ class KPlanesTrainer(FusedStep):
                 ws = self._mlp_ws.get("field.sigma")
                 if ws is not None:
                     self._ws_dirty.add("field.sigma")
-                fnq = self.lib.snerf_mlp_bwd_x16_quotient_ws if ws is not None else self.lib.snerf_mlp_bwd_x16_quotient
-                _lib.check(fnq(C.byref(self.sigma_net.desc), self._p(self.sigma_net.params), self._p(b["feat16"]), F, C.c_int64(N),
-                               self._p(b["gh"]), 16, 15, self._p(b["gdens"][2]), self._p(ss.G), F, self._p(ss.fix_list),
-                               ss.fix_capacity, self._p(ss.fix_count), self._p(ss.fix_counts[1 - k:2 - k]),
-                               self._p(ws if ws is not None else self.gviews["field.sigma"]), self._st), "mlp_bwd_x16_quotient")
+                self._call("mlp_bwd_x16_quotient_ws" if ws is not None else "mlp_bwd_x16_quotient",
+                           C.byref(self.sigma_net.desc), self._p(self.sigma_net.params), self._p(b["feat16"]), F, N,
+                           self._p(b["gh"]), 16, 15, self._p(b["gdens"][2]), self._p(ss.G), F, self._p(ss.fix_list),
+                           ss.fix_capacity, self._p(ss.fix_count), self._p(ss.fix_counts[1 - k:2 - k]),
+                           self._p(ws if ws is not None else self.gviews["field.sigma"]), self._st)
         else:
             self._mlp_bwd(self.sigma_net, "field.sigma", sl(b["feat16"] if self._fwd_fused else b["feat"]), F, N, sl(b["gh"]), 16, 15, b["gdens"][2][r0:r1],
                           sl(b["gfeat"]), F, x16=self._fwd_fused)
@@ -720,8 +718,8 @@ class KPlanesTrainer(FusedStep):
                         self._reg_zeroed = True
             else:
               with self._span("kplanes_gradvec.field"):
-                _lib.check(self.lib.snerf_kplanes_gradvec(C.byref(ss.desc), self._p(self.field_planes.planes), C.byref(co), C.c_int64(ss.N),
-                                                          self._p(b["gfeat"]), self._p(ss.gvec), ss.gvec_bf16, self._st), "gradvec")
+                self._call("kplanes_gradvec", C.byref(ss.desc), self._p(self.field_planes.planes), C.byref(co), ss.N,
+                           self._p(b["gfeat"]), self._p(ss.gvec), ss.gvec_bf16, self._st)
             if self._sharded() and len(self._exchange) == 2:
                 # finest scale first: its reduce-scatter (chunk 0) is on the links while the coarser scales are still being scattered
                 self._scatter_field_scales(co, ns - 1, ns)
@@ -755,9 +753,9 @@ class KPlanesTrainer(FusedStep):
             return
         cfg, b, R = self.cfg, self.buf, self.R
         dn = None if cfg.is_euclidean_depth else self.rays["directions_norm"]
-        _lib.check(self.lib.snerf_depth_loss(self._p(b["w"][lvl]), self._p(b["eb"][lvl]), self._p(self._depth), self._p(dn) if dn is not None else None,
-                                             cfg.depth_sigma, R, self.S[lvl], cfg.loss_coefficients["depth_loss"] / (3 * R), self._p(b["depth_rays"][lvl]),
-                                             self._p(b["gw"][lvl]) if with_grad else None, 1, self._st), "depth_loss")
+        self._call("depth_loss", self._p(b["w"][lvl]), self._p(b["eb"][lvl]), self._p(self._depth), self._p(dn) if dn is not None else None,
+                   cfg.depth_sigma, R, self.S[lvl], cfg.loss_coefficients["depth_loss"] / (3 * R), self._p(b["depth_rays"][lvl]),
+                   self._p(b["gw"][lvl]) if with_grad else None, 1, self._st)
 
     def _proposal_backward(self, proposal_grads: bool):
         """Proposal supervision (interlevel loss); gradients only on `updated` steps (ray_samplers.py:573,587-592).  The two levels touch disjoint
@@ -790,7 +788,7 @@ class KPlanesTrainer(FusedStep):
                 L.gX = b["gpfeat"][lvl].data_ptr() if cfg.ray_gradients else None
                 self._ws_dirty.add(f"prop{lvl}.mlp")
             with self._span("kplanes_density_bwd"):
-                _lib.check(self.lib.snerf_kplanes_density_bwd(levels, 2, self._st), "kplanes_density_bwd")
+                self._call("kplanes_density_bwd", levels, 2, self._st)
         elif cfg.interleave_proposal_levels:
             for stage in (wb, nb, sc):
                 for lvl in (0, 1):
@@ -808,9 +806,8 @@ class KPlanesTrainer(FusedStep):
     def _ray_gradient(self, desc, planes, coords, N, gfeat):
         """ray_grads += d(sum gfeat . features) / d(ray origins, directions) of one sampling level (snerf_kplanes_gather_bwd_coords)."""
         with self._span("kplanes_gather_bwd_coords.field" if desc is self._desc_field else "kplanes_gather_bwd_coords.prop"):
-            _lib.check(self.lib.snerf_kplanes_gather_bwd_coords(C.byref(desc), self._p(planes), C.byref(coords), C.c_int64(N), self._p(gfeat), None,
-                                                                self._p(self.ray_grads["origins"]), self._p(self.ray_grads["directions"]), self._st),
-                       "kplanes_gather_bwd_coords")
+            self._call("kplanes_gather_bwd_coords", C.byref(desc), self._p(planes), C.byref(coords), N, self._p(gfeat), None,
+                       self._p(self.ray_grads["origins"]), self._p(self.ray_grads["directions"]), self._st)
 
     def backward(self, target: torch.Tensor, rng: Dict[str, torch.Tensor], proposal_grads: bool, include_reg: bool = True,
                  defer_prop_join: bool = False, depth: Optional[torch.Tensor] = None):

@@ -39,7 +39,12 @@ typedef void* snerf_stream_t; /* hipStream_t */
  * revision-2 library from before them fails at load with the usual "rebuild the library" error, not at the first call.
  * The same holds for snerf_mask_pack and snerf_sample_pixels_masked (pixel draws inside image masks), and for snerf_kplanes_gather_bwd_coords,
  * snerf_pose_apply and snerf_raygen_pose_bwd (the camera optimiser: coordinate gradients of the plane gather down to SO3xR3 pose deltas), and for
- * snerf_ray_time_order and snerf_kplanes_field_fwd_ordered (the fused field forward's tiles walked in order of frame time). */
+ * snerf_ray_time_order and snerf_kplanes_field_fwd_ordered (the fused field forward's tiles walked in order of frame time).
+ * NOT so for snerf_coords.contract (the L-inf scene contraction): it names a slot that was padding -- size, offsets and the meaning of 0 are
+ * unchanged -- and adds no symbol, so a revision-2 library built BEFORE it loads under a binding that knows the field, ignores contract = 1 and
+ * normalises by whatever box the caller left (a zero box for ops.coords_from_rays(aabb=None)).  No symbol check catches that, so the Python
+ * binding asks the library once at load: snerf_kplanes_gather_fwd with contract = 2 and N = 0 must be refused (an older library returns 0) and
+ * a library that accepts it is refused with the usual "rebuild the library" error.  A C caller that sets contract = 1 should make the same call. */
 #define SNERF_ABI_REVISION 2
 
 /* Library identity / diagnostics. */
@@ -71,12 +76,18 @@ typedef struct {
  *         SceneBox.get_normalized_positions (NS/data/scene_box.py:55-65) and the time rescale
  *         (kplanes_field.py:283-291): pos = o + d*(e[s]+e[s+1])/2; p = (pos-aabb_min)/(aabb_max-aabb_min);
  *         if rescale: p = 2p-1 (main field) else p stays in [0,1] (proposal field quirk, :440);
- *         t = 2*time-1.  N = R*S, sample n = ray n/S, bin n%S. */
+ *         t = 2*time-1.  N = R*S, sample n = ray n/S, bin n%S.
+ *         contract = 1 (unbounded scenes; the slot was padding and 0 keeps every bit of the above): in place of the box normalisation,
+ *         SceneContraction(order=inf) (NS/field_components/spatial_distortions.py:42-89) and the fields' halving (kplanes_field.py:278-280,
+ *         :438-440): m = max_k |pos_k|; y = m < 1 ? pos : (2 - 1/m) * (pos / m); p = y / 2 -- that float32 expression operation by operation
+ *         (IEEE division, no fused multiply-add; m == 1 takes the second branch).  aabb_min, aabb_max and rescale are not read; t is as above.
+ *         Every entry that takes a snerf_coords refuses, before any launch, a contract outside {0, 1} and contract = 1 with mode 0 (those points
+ *         are already final).  The temporal-grid entries (snerf_tgrid_*) derive their coordinates themselves and refuse contract != 0. */
 typedef struct {
   int32_t mode;
   int32_t S;             /* samples per ray (mode 1) */
   int32_t rescale;       /* mode 1: 1 = map [0,1] -> [-1,1] */
-  int32_t _pad;
+  int32_t contract;      /* mode 1: 0 = none; 1 = L-inf scene contraction (see above: aabb_* and rescale are then not read) */
   const float* pts;      /* mode 0: [N,4]; [N,3] with a 3-coordinate descriptor */
   const float* origins;  /* mode 1: [R,3] */
   const float* dirs;     /* mode 1: [R,3] */
@@ -110,6 +121,11 @@ int snerf_kplanes_gather_bwd(const snerf_kplanes_desc* desc, const float* planes
  *   grad_origins, grad_dirs [R,3]  ACCUMULATED (+=), mode 1 only: g_o += k sum_s g_p(s), g_d += k sum_s tmid(s) g_p(s) with
  *                           tmid = (e[s] + e[s+1]) / 2 and k = (rescale ? 2 : 1) / (aabb_max - aabb_min) per axis.  Time carries no gradient
  *                           to the ray.  The sum over a ray's samples runs in a fixed order, without atomics: two runs give the same bits.
+ *                           With coords.contract = 1, k is 1 and each sample's g_p first goes through the contraction's Jacobian transposed:
+ *                           h = g_p / 2 inside (m < 1); outside, with j the FIRST axis whose |pos_j| equals m,
+ *                           h_k = (a g_k + [k == j] b sum_i pos_i g_i) / 2, a = 2/m - 1/m^2, b = (-2/m^2 + 2/m^3) sign(pos_j).
+ *                           (On a tie of two axes autograd splits the max's gradient evenly; a tie has measure zero and the first index is
+ *                           taken here.)  grad_pts stays the derivative w.r.t. p.
  * Semantics are ATen's for bilinear, align_corners=True, border padding: along an axis the slope is (W - 1) / 2 times the difference of the two
  * texel columns weighted by the other axis; zero where the unnormalised coordinate is clipped (<= 0 or >= W - 1), so also for a resolution of 1.
  * DELIBERATE DEVIATION: the bin edges e[] are constants.  The reference's autograd also differentiates the collider's nears / fars (and with

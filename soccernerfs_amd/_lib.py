@@ -31,7 +31,7 @@ class Coords(C.Structure):
         ("mode", C.c_int32),
         ("S", C.c_int32),
         ("rescale", C.c_int32),
-        ("_pad", C.c_int32),
+        ("contract", C.c_int32),
         ("pts", C.c_void_p),
         ("origins", C.c_void_p),
         ("dirs", C.c_void_p),
@@ -323,6 +323,16 @@ def bind(path: str):
         raise RuntimeError(f"libsnerf ABI {l.snerf_abi_version()} != binding {ABI_VERSION}: rebuild the library")
     if l.snerf_abi_revision() != ABI_REVISION:
         raise RuntimeError(f"libsnerf ABI {ABI_VERSION} revision {l.snerf_abi_revision()} != binding revision {ABI_REVISION}: rebuild the library")
+    # snerf_coords.contract took the struct's padding slot without a new symbol or revision: a library from before it would load and IGNORE the
+    # field.  One host-side call tells them apart -- this header's library refuses contract = 2 before it looks at anything else that is empty
+    # here (N = 0: nothing is launched either way), an older one returns success.
+    desc, coords = KPlanesDesc(), Coords()
+    desc.n_scales, desc.C, desc.n_coords = 1, 8, 3
+    for k in range(3):
+        desc.res[0][k] = 1
+    coords.mode, coords.S, coords.contract = 1, 1, 2
+    if l.snerf_kplanes_gather_fwd(C.byref(desc), None, C.byref(coords), 0, None, None) == 0:
+        raise RuntimeError(f"libsnerf at {path} predates snerf_coords.contract (it accepts contract = 2): rebuild the library")
     return l
 
 

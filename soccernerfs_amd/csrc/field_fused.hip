@@ -22,38 +22,7 @@ namespace snerf {
 
 // field_fwd_kernel itself is defined in field_fused_common.hpp (a template over the plane count as well: field_fused_static.hip builds NP = 3).
 
-// The same tiles walked in the order of a ray permutation (snerf_kplanes_field_fwd_ordered: coords.mode = 1 and S % 32 == 0, so a tile is 32 samples
-// of ONE ray): with tpr = S / 32, tile k of the walk is sub-tile k % tpr of ray ray_order[k / tpr].  All samples of a ray share t, so with the rays in
-// order of frame time the tiles resident at one moment read the same two texel rows of every XT / YT / ZT plane.  Every sample's outputs go to that
-// sample's own rows, whatever the walk: the results are those of field_fwd_kernel bit for bit.  A kernel of its own, so that field_fwd_kernel keeps
-// its arguments and its registers.
-template <typename T, int NS, int KEEP = 0, bool VD = false>
-__global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_ordered_kernel(FieldArgs a, uint32_t n_tiles, const int32_t* __restrict__ ray_order,
-                                                                          uint32_t tpr) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* smem = reinterpret_cast<T*>(smem_raw);
-  typename Ops<T>::v8 breg[NS];
-  uint32_t k = blockIdx.x, k_end = n_tiles, step = gridDim.x;  // fewer than 8 workgroups: a plain stride over the ordered tiles
-  // Workgroups with equal blockIdx.x % 8 share an XCD, and so an L2: group x walks the x-th contiguous eighth of the ordered tiles, gridDim.x / 8
-  // members striding inside it, so that each L2 holds the rows of its own range of frame times, however many frames the batch spans.  Placement is
-  // affinity only: the eight ranges tile [0, n_tiles) whatever runs where.  (The launcher makes the grid a multiple of 8; workgroups past the last
-  // whole eight would have no place.)  Against a plain stride over the whole list, where every L2 sees the same one or two frame times: 274.5-274.8
-  // against 276.3-276.8 us alone at the preset, 0.836 against 0.845 GB fetched (profiles/r23_fwd_order_INDEX.md).
-  if (gridDim.x >= 8) {
-    const uint32_t x = blockIdx.x & 7;
-    step = gridDim.x >> 3;
-    if ((blockIdx.x >> 3) >= step) return;
-    k = (uint32_t)((uint64_t)x * n_tiles >> 3) + (blockIdx.x >> 3);
-    k_end = (uint32_t)((uint64_t)(x + 1) * n_tiles >> 3);
-  }
-  field_stage_weights<T, NS, VD>(a, smem, breg);
-  for (; k < k_end; k += step) {
-    const uint32_t r = k / tpr, sub = k - r * tpr;
-    field_tile<T, NS, KEEP, VD>(
-        a, ((int64_t)ray_order[r] * tpr + sub) * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
-        [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
-  }
-}
+// field_fwd_ordered_kernel, the same tiles walked in the order of a ray permutation, is defined there as well.
 
 int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N, const snerf_mlp_desc* sd, const snerf_mlp_desc* cd,
                    int max_scales) {
@@ -70,6 +39,7 @@ int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N
                 "kplanes_field: the fused kernels compute with bf16 / fp16 MFMA operands (operands = 1 / 2, both nets alike); fp32 runs unfused");
   SNERF_REQUIRE(N >= 0 && N < (1LL << 31), "kplanes_field: N=%lld", (long long)N);
   SNERF_REQUIRE(c->mode == 0 || c->mode == 1, "kplanes_field: coords.mode=%d", c->mode);
+  SNERF_REQUIRE_CONTRACT(c, "kplanes_field");
   if (c->mode == 1) SNERF_REQUIRE(c->S >= 1 && N % c->S == 0, "kplanes_field: N=%lld not a multiple of S=%d", (long long)N, c->S);
   if (cd->d_in != FF_GEO && N > 0) SNERF_REQUIRE(c->mode == 1, "kplanes_field: the view-dependent colour net reads per-ray directions (coords.mode = 1)");
   // the kernels dereference these: a static scene (three coordinates) has no times, every other ray buffer and a 4-coordinate descriptor's times must be there
@@ -138,6 +108,7 @@ extern "C" int snerf_kplanes_field_fwd_ordered(const snerf_kplanes_desc* desc, c
   SNERF_REQUIRE((feat16 != nullptr) == (h != nullptr) && (!feat32 || feat16),
                 "kplanes_field_fwd: the training outputs come as a set: feat16 and h together, feat32 only with them");
   a.feat16 = feat16; a.h = h; a.feat32 = feat32;
+  if (coords->contract) return launch_field_fwd_contract(a, sigma->operands, ray_order, (hipStream_t)stream, color->d_in != FF_GEO);
   if (desc->n_coords == 3) return launch_field_fwd_static(a, sigma->operands, (hipStream_t)stream, color->d_in != FF_GEO);
   FF_DISPATCH_FWD(launch_field_fwd, sigma->operands, desc->n_scales, a, ray_order, (hipStream_t)stream, color->d_in != FF_GEO);
 }

@@ -87,7 +87,7 @@ __device__ __forceinline__ void load_breg(const float* __restrict__ W0, int wave
 }
 
 // gather phase: 16 lanes per sample = (4-channel group cg) x (scale parity sg); rounds the features into the A-operand image XS
-template <typename T, int NS, bool F32OUT = false, int NP = 6>
+template <typename T, int NS, bool F32OUT = false, int NP = 6, int CT = 0>
 __device__ __forceinline__ void gather_tile(const FieldArgs& a, int64_t n0, T* XS) {
   using P = PlanFF<NS>;
   // waves 0-3 take the even scales, waves 4-7 the odd ones: the scale index is wave-uniform, so the descriptor reads stay scalar
@@ -95,7 +95,7 @@ __device__ __forceinline__ void gather_tile(const FieldArgs& a, int64_t n0, T* X
   const int64_t n = n0 + sample;
   float p[4];
   const bool live = n < a.N;
-  if (live) load_coords<NP>(a.c, n, p);
+  if (live) load_coords<NP, CT>(a.c, n, p);
 #pragma unroll 1  // one scale's 24 texel reads in flight at a time: unrolled, the three scales' loads cost ~160 VGPRs and the occupancy the kernel lives on
   for (int s = sg; s < NS; s += 2) {
     float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -149,7 +149,10 @@ __device__ __forceinline__ void field_stage_weights(const FieldArgs& a, T* smem,
 // KEEP: what a training step leaves behind for its backward -- 0 nothing (eval), 1 the 16-bit feature tile + the sigma_net outputs,
 // 2 those + the fp32 features (quotient scatter).  Compile-time: as run-time pointer tests these cost every variant registers.
 // NP: planes per scale, 6 or 3 (a 3-coordinate descriptor); a template parameter too, so that the six-plane tile is the code it was.
-template <typename T, int NS, int KEEP, bool VD, int NP = 6, typename DensSink, typename RgbSink>
+// CT: 1 = contracted coordinates (snerf_coords.contract, load_coords_ray); a template parameter for the same reason -- these kernels sit at
+// their register limit and the run-time branch cost several instantiations spilled registers.  The CT = 1 kernels are built by
+// field_fused_contract.hip and render_eval_contract.hip.
+template <typename T, int NS, int KEEP, bool VD, int NP = 6, int CT = 0, typename DensSink, typename RgbSink>
 __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* smem, const typename Ops<T>::v8 (&breg)[NS], DensSink&& dens_sink,
                                            RgbSink&& rgb_sink) {
   using P = PlanFF<NS>;
@@ -158,7 +161,7 @@ __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* sm
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   T *XS = smem + P::XS, *A1 = smem + P::A1, *CX = smem + P::CX, *CA1 = smem + P::XS, *CA2 = smem + P::XS + FF_TS * P::LKC;
   __syncthreads();  // weights staged / the previous tile's colour layers have read CA1, CA2 (= XS)
-  gather_tile<T, NS, KEEP == 2, NP>(a, n0, XS);
+  gather_tile<T, NS, KEEP == 2, NP, CT>(a, n0, XS);
   if constexpr (VD) {  // one SH coefficient per thread: 32 samples x 16 (the previous tile's colour layer 0 read CX before the loop-top barrier)
     const int sample = threadIdx.x >> 4, k = threadIdx.x & 15;
     const int64_t n = n0 + sample;
@@ -222,16 +225,49 @@ __device__ __forceinline__ void field_tile(const FieldArgs& a, int64_t n0, T* sm
 
 // The forward kernel (field_fused.hip describes it): a persistent workgroup strides over the tiles; density and colour go to HBM.  NP = 6 is
 // instantiated by field_fused.hip, NP = 3 (a 3-coordinate descriptor) by field_fused_static.hip.
-template <typename T, int NS, int KEEP = 0, bool VD = false, int NP = 6>
+template <typename T, int NS, int KEEP = 0, bool VD = false, int NP = 6, int CT = 0>
 __global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_kernel(FieldArgs a, int64_t n_tiles) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   typename Ops<T>::v8 breg[NS];
   field_stage_weights<T, NS, VD>(a, smem, breg);
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    field_tile<T, NS, KEEP, VD, NP>(
+    field_tile<T, NS, KEEP, VD, NP, CT>(
         a, tile * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
         [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
+}
+
+// The same tiles walked in the order of a ray permutation (snerf_kplanes_field_fwd_ordered: coords.mode = 1 and S % 32 == 0, so a tile is 32 samples
+// of ONE ray): with tpr = S / 32, tile k of the walk is sub-tile k % tpr of ray ray_order[k / tpr].  All samples of a ray share t, so with the rays in
+// order of frame time the tiles resident at one moment read the same two texel rows of every XT / YT / ZT plane.  Every sample's outputs go to that
+// sample's own rows, whatever the walk: the results are those of field_fwd_kernel bit for bit.  A kernel of its own, so that field_fwd_kernel keeps
+// its arguments and its registers.
+template <typename T, int NS, int KEEP = 0, bool VD = false, int CT = 0>
+__global__ __launch_bounds__(FF_NW * 64, 4) void field_fwd_ordered_kernel(FieldArgs a, uint32_t n_tiles, const int32_t* __restrict__ ray_order,
+                                                                          uint32_t tpr) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  typename Ops<T>::v8 breg[NS];
+  uint32_t k = blockIdx.x, k_end = n_tiles, step = gridDim.x;  // fewer than 8 workgroups: a plain stride over the ordered tiles
+  // Workgroups with equal blockIdx.x % 8 share an XCD, and so an L2: group x walks the x-th contiguous eighth of the ordered tiles, gridDim.x / 8
+  // members striding inside it, so that each L2 holds the rows of its own range of frame times, however many frames the batch spans.  Placement is
+  // affinity only: the eight ranges tile [0, n_tiles) whatever runs where.  (The launcher makes the grid a multiple of 8; workgroups past the last
+  // whole eight would have no place.)  Against a plain stride over the whole list, where every L2 sees the same one or two frame times: 274.5-274.8
+  // against 276.3-276.8 us alone at the preset, 0.836 against 0.845 GB fetched (profiles/r23_fwd_order_INDEX.md).
+  if (gridDim.x >= 8) {
+    const uint32_t x = blockIdx.x & 7;
+    step = gridDim.x >> 3;
+    if ((blockIdx.x >> 3) >= step) return;
+    k = (uint32_t)((uint64_t)x * n_tiles >> 3) + (blockIdx.x >> 3);
+    k_end = (uint32_t)((uint64_t)(x + 1) * n_tiles >> 3);
+  }
+  field_stage_weights<T, NS, VD>(a, smem, breg);
+  for (; k < k_end; k += step) {
+    const uint32_t r = k / tpr, sub = k - r * tpr;
+    field_tile<T, NS, KEEP, VD, 6, CT>(
+        a, ((int64_t)ray_order[r] * tpr + sub) * FF_TS, smem, breg, [&](int, int64_t n, float v) { a.dens[n] = v; },
+        [&](int, int64_t n, int col, float v) { a.rgb[n * 3 + col] = v; });
+  }
 }
 
 // grid of the persistent forward: two 8-wave workgroups per CU where the LDS plan allows (125 VGPRs)
@@ -248,6 +284,9 @@ int validate_field(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t N
 
 // the unordered forward for a 3-coordinate descriptor (field_fused_static.hip: the NP = 3 instantiations in a translation unit of their own)
 int launch_field_fwd_static(const FieldArgs& a, int operands, hipStream_t st, bool vd);
+
+// the forward with contracted coordinates (a.c.contract = 1), six or three planes, ordered walk included (field_fused_contract.hip)
+int launch_field_fwd_contract(const FieldArgs& a, int operands, const int32_t* ray_order, hipStream_t st, bool vd);
 
 #define FF_DISPATCH(FN, operands, ns, ...)                                                   \
   do {                                                                                       \

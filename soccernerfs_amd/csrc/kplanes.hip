@@ -176,6 +176,7 @@ static int validate(const snerf_kplanes_desc* d, const snerf_coords* c, int64_t 
   SNERF_REQUIRE(d->C == 8 || d->C == 16 || d->C == 32, "kplanes: C=%d unsupported (8, 16, 32)", d->C);
   SNERF_REQUIRE(d->n_coords == 3 || d->n_coords == 4, "kplanes: n_coords=%d unsupported", d->n_coords);
   SNERF_REQUIRE(N >= 0, "kplanes: negative N");
+  SNERF_REQUIRE_CONTRACT(c, "kplanes");
   for (int s = 0; s < d->n_scales; ++s)
     for (int k = 0; k < d->n_coords; ++k) SNERF_REQUIRE(d->res[s][k] >= 1, "kplanes: res[%d][%d]=%d", s, k, d->res[s][k]);
   if (c->mode == 0) {

@@ -30,17 +30,51 @@ __device__ __forceinline__ AxisTap tap_from_pix(float fx, int size) {
 }
 __device__ __forceinline__ AxisTap axis_tap(float x, int size) { return tap_from_pix(axis_pix(x, size), size); }
 
-// coordinate of sample s of ray r (snerf_coords mode 1: positions derived from rays + euclidean bin edges).  NP = 3 (static scene): there is no
-// time axis and c.times, which may be null then, is never read.
-template <int NP = 6>
-__device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r, int s, float p[4]) {
+// Euclidean position of sample s of ray r: Frustums.get_positions, o + (d * (e[s] + e[s+1])) / 2 in that order
+__device__ __forceinline__ void ray_position(const snerf_coords& c, int64_t r, int s, float pos[3]) {
   const float* eb = c.ebins + r * (c.S + 1) + s;
-  float mid = eb[0] + eb[1];
+  const float mid = eb[0] + eb[1];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pos[k] = c.origins[r * 3 + k] + (c.dirs[r * 3 + k] * mid) / 2.f;
+}
+
+// snerf_coords.contract = 1: SceneContraction(order=inf) and the K-Planes fields' halving, evaluated as the elementwise
+// float32 expression  where(m < 1, pos, (2 - 1 / m) * (pos / m)) / 2  with m = max_k |pos_k|: every operation rounds on its own (no fused
+// multiply-add, IEEE division), so the coordinate has the bits of that expression and of every other kernel's recomputation of it.
+// m == 1 takes the second branch (it returns pos there as well: 2 - 1 = 1, pos / 1 = pos).
+__device__ __forceinline__ void contract_inf_half(const float pos[3], float p[4]) {
+#pragma clang fp contract(off)
+  const float m = fmaxf(fmaxf(fabsf(pos[0]), fabsf(pos[1])), fabsf(pos[2]));
+  const bool inside = m < 1.f;
+  const float f = 2.f - 1.f / m;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    float pos = c.origins[r * 3 + k] + (c.dirs[r * 3 + k] * mid) / 2.f;
-    float q = (pos - c.aabb_min[k]) / (c.aabb_max[k] - c.aabb_min[k]);
-    p[k] = c.rescale ? q * 2.f - 1.f : q;
+    const float y = inside ? pos[k] : f * (pos[k] / m);
+    p[k] = y / 2.f;
+  }
+}
+
+// coordinate of sample s of ray r (snerf_coords mode 1: positions derived from rays + euclidean bin edges).  NP = 3 (static scene): there is no
+// time axis and c.times, which may be null then, is never read.
+// CT: where the contraction switch is decided.  -1 = at run time: c.contract is uniform over a launch and sits in the argument block, a scalar
+// branch.  0 / 1 = at compile time, for the kernel families that live at their register limit (the fused field forward, its ordered walk and the
+// render tail; the fused proposal backward; the coordinate gradient), where the run-time branch cost spilled registers or an occupancy step
+// (DESIGN.md 4.15): their launchers pick the instantiation from coords.contract, and with CT = 0 the function is the text it always was.
+template <int NP = 6, int CT = -1>
+__device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r, int s, float p[4]) {
+  if (CT > 0 || (CT < 0 && c.contract)) {
+    float pos[3];
+    ray_position(c, r, s, pos);
+    contract_inf_half(pos, p);
+  } else {
+    const float* eb = c.ebins + r * (c.S + 1) + s;
+    float mid = eb[0] + eb[1];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float pos = c.origins[r * 3 + k] + (c.dirs[r * 3 + k] * mid) / 2.f;
+      float q = (pos - c.aabb_min[k]) / (c.aabb_max[k] - c.aabb_min[k]);
+      p[k] = c.rescale ? q * 2.f - 1.f : q;
+    }
   }
   if constexpr (NP == 6) p[3] = c.times[r] * 2.f - 1.f;
   else p[3] = 0.f;
@@ -49,8 +83,21 @@ __device__ __forceinline__ void load_coords_ray(const snerf_coords& c, int64_t r
 // host: the ray buffers of mode-1 coordinates are all there.  A 4-coordinate descriptor needs the rays' times; a static scene has none to give.
 inline bool ray_coords_complete(const snerf_coords* c, int n_coords) { return c->origins && c->dirs && c->ebins && (c->times || n_coords == 3); }
 
+// host: what every entry that takes a snerf_coords checks about its contraction switch before it launches anything.  Returns the complaint,
+// or null when the descriptor is fine.
+inline const char* coords_contract_complaint(const snerf_coords* c) {
+  if (c->contract != 0 && c->contract != 1) return "coords.contract must be 0 (none) or 1 (L-inf scene contraction)";
+  if (c->contract == 1 && c->mode != 1) return "coords.contract = 1 needs coords.mode 1 (rays): the points of mode 0 are already final";
+  return nullptr;
+}
+#define SNERF_REQUIRE_CONTRACT(c, who)                                                     \
+  do {                                                                                     \
+    const char* complaint_ = snerf::coords_contract_complaint(c);                          \
+    SNERF_REQUIRE(complaint_ == nullptr, "%s: %s (contract=%d, mode=%d)", who, complaint_ ? complaint_ : "", (c)->contract, (c)->mode); \
+  } while (0)
+
 // coordinate of sample n along x,y,z,t in grid_sample's [-1,1] convention
-template <int NP>
+template <int NP, int CT = -1>
 __device__ __forceinline__ void load_coords(const snerf_coords& c, int64_t n, float p[4]) {
   if (c.mode == 0) {
     if (NP == 6) {
@@ -62,7 +109,7 @@ __device__ __forceinline__ void load_coords(const snerf_coords& c, int64_t n, fl
   } else {
     int64_t r = n / c.S;  // a 64-bit software division (~100 instructions): loops over consecutive samples step (r, s) themselves
     int s = (int)(n - r * c.S);
-    load_coords_ray<NP>(c, r, s, p);
+    load_coords_ray<NP, CT>(c, r, s, p);
   }
 }
 

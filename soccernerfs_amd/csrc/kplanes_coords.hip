@@ -54,9 +54,31 @@ __device__ __forceinline__ void plane_sample_slopes(const float* __restrict__ ba
                    (sw.z - nw.z) * tx.w0 + (se.z - ne.z) * tx.w1, (sw.w - nw.w) * tx.w0 + (se.w - ne.w) * tx.w1);
 }
 
+// g (the gradient w.r.t. p = contract_inf_half(pos), first three components) -> the gradient w.r.t. pos: the contraction's Jacobian
+// transposed.  Inside (m < 1) p = pos / 2.  Outside p_k = f(m) pos_k / 2 with f = 2/m - 1/m^2 and m = |pos_j|:
+//   h_k = (f g_k + [k == j] f'(m) sign(pos_j) sum_i pos_i g_i) / 2,   f' = -2/m^2 + 2/m^3.
+// j is the FIRST axis that attains the maximum (autograd splits a tie evenly; ties have measure zero).  m == 1 goes outside, as in the forward.
+__device__ __forceinline__ void contract_inf_half_vjp(const float pos[3], float g[4]) {
+  const float a0 = fabsf(pos[0]), a1 = fabsf(pos[1]), a2 = fabsf(pos[2]);
+  const float m = fmaxf(fmaxf(a0, a1), a2);
+  if (m < 1.f) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[k] = g[k] / 2.f;
+    return;
+  }
+  const int j = a0 == m ? 0 : (a1 == m ? 1 : 2);
+  const float pj = j == 0 ? pos[0] : (j == 1 ? pos[1] : pos[2]);
+  const float a = 2.f / m - 1.f / (m * m);
+  const float b = (-2.f / (m * m) + 2.f / (m * m * m)) * (pj < 0.f ? -1.f : 1.f);
+  const float dot = (pos[0] * g[0] + pos[1] * g[1]) + pos[2] * g[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) g[k] = (a * g[k] + (k == j ? b * dot : 0.f)) / 2.f;
+}
+
 constexpr int COORDS_BLOCK_STEPS = 4;  // mode 0: a wavefront takes 4 steps of its 64 / LPS lane groups
 
-template <int C, int NP>
+// CT: 1 = contracted coordinates (snerf_coords.contract).  Compile time: as a run-time branch it cost the six-plane kernel an occupancy step.
+template <int C, int NP, int CT = 0>
 __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kplanes_desc d, const float* __restrict__ planes, snerf_coords c,
                                                                        int64_t N, const float* __restrict__ gout, float* __restrict__ gpts,
                                                                        float* __restrict__ g_origins, float* __restrict__ g_dirs) {
@@ -78,10 +100,12 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kp
     const bool active = i < per && n < N;
     float gp[4] = {0.f, 0.f, 0.f, 0.f};
     float tmid = 0.f;
+    float pos[3] = {0.f, 0.f, 0.f};  // contract = 1: the sample's Euclidean position, for the contraction's Jacobian
     if (active) {
       float p[4];
       if (c.mode == 1) {
-        load_coords_ray<NP>(c, owner, i, p);
+        load_coords_ray<NP, CT>(c, owner, i, p);
+        if constexpr (CT == 1) ray_position(c, owner, i, pos);
         const float* eb = c.ebins + owner * (c.S + 1) + i;
         tmid = (eb[0] + eb[1]) / 2.f;
       } else {
@@ -121,6 +145,7 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kp
 #pragma unroll
         for (int k = 0; k < NC; ++k) gpts[n * NC + k] = gp[k];
       }
+      if constexpr (CT == 1) contract_inf_half_vjp(pos, gp);  // gp[0..2] become d / d(pos), written to grad_pts above as d / d(p)
 #pragma unroll
       for (int k = 0; k < 3; ++k) { ro[k] += gp[k]; rd[k] += tmid * gp[k]; }
     }
@@ -137,7 +162,7 @@ __global__ __launch_bounds__(256) void kplanes_gather_bwd_coords_kernel(snerf_kp
   }
   if (lane < 3) {  // selects, not a lane-indexed read of the argument block (that would copy it to scratch)
     const float ext = lane == 0 ? c.aabb_max[0] - c.aabb_min[0] : lane == 1 ? c.aabb_max[1] - c.aabb_min[1] : c.aabb_max[2] - c.aabb_min[2];
-    const float scale = (c.rescale ? 2.f : 1.f) / ext;
+    const float scale = CT == 1 ? 1.f : (c.rescale ? 2.f : 1.f) / ext;  // contracted: the Jacobian went in per sample, the box is not read
     const float so = lane == 0 ? ro[0] : lane == 1 ? ro[1] : ro[2];
     const float sd = lane == 0 ? rd[0] : lane == 1 ? rd[1] : rd[2];
     if (g_origins) g_origins[owner * 3 + lane] += scale * so;
@@ -150,7 +175,10 @@ static int launch_bwd_coords(const snerf_kplanes_desc* d, const float* planes, c
                              float* go, float* gd, hipStream_t st) {
   const int64_t per = c->mode == 1 ? c->S : (64 / (C / 4)) * COORDS_BLOCK_STEPS;
   const int64_t owners = (N + per - 1) / per;
-  hipLaunchKernelGGL((kplanes_gather_bwd_coords_kernel<C, NP>), dim3(ceil_div(owners, 4)), dim3(256), 0, st, *d, planes, *c, N, gout, gpts, go, gd);
+  if (c->contract)
+    hipLaunchKernelGGL((kplanes_gather_bwd_coords_kernel<C, NP, 1>), dim3(ceil_div(owners, 4)), dim3(256), 0, st, *d, planes, *c, N, gout, gpts, go, gd);
+  else
+    hipLaunchKernelGGL((kplanes_gather_bwd_coords_kernel<C, NP, 0>), dim3(ceil_div(owners, 4)), dim3(256), 0, st, *d, planes, *c, N, gout, gpts, go, gd);
   SNERF_LAUNCH_CHECK("kplanes_gather_bwd_coords");
   return 0;
 }
@@ -168,6 +196,7 @@ extern "C" int snerf_kplanes_gather_bwd_coords(const snerf_kplanes_desc* desc, c
   SNERF_REQUIRE(desc->C == 8 || desc->C == 16 || desc->C == 32, "kplanes_gather_bwd_coords: C=%d unsupported (8, 16, 32)", desc->C);
   SNERF_REQUIRE(desc->n_coords == 3 || desc->n_coords == 4, "kplanes_gather_bwd_coords: n_coords=%d unsupported", desc->n_coords);
   SNERF_REQUIRE(N >= 0, "kplanes_gather_bwd_coords: negative N");
+  SNERF_REQUIRE_CONTRACT(coords, "kplanes_gather_bwd_coords");
   for (int s = 0; s < desc->n_scales; ++s)
     for (int k = 0; k < desc->n_coords; ++k) SNERF_REQUIRE(desc->res[s][k] >= 1, "kplanes_gather_bwd_coords: res[%d][%d]=%d", s, k, desc->res[s][k]);
   if (coords->mode == 0) {

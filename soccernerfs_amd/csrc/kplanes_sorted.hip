@@ -791,6 +791,7 @@ static int check_desc(const snerf_kplanes_desc* d, const snerf_coords* c, int64_
   SNERF_REQUIRE(d->n_coords == 3 || d->n_coords == 4, "kplanes_sorted: n_coords=%d", d->n_coords);
   SNERF_REQUIRE(N >= 0 && N < (1LL << 31), "kplanes_sorted: N=%lld", (long long)N);
   SNERF_REQUIRE(c->mode == 0 || c->mode == 1, "kplanes_sorted: coords.mode=%d", c->mode);
+  SNERF_REQUIRE_CONTRACT(c, "kplanes_sorted");
   if (c->mode == 1 && N > 0)
     SNERF_REQUIRE(ray_coords_complete(c, d->n_coords), "kplanes_sorted: null ray buffers (times may be null only with three coordinates)");
   return 0;

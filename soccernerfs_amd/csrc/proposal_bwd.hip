@@ -87,7 +87,9 @@ __device__ __forceinline__ V pick6(int q, V v0, V v1, V v2, V v3, V v4, V v5) {
 }
 
 // two waves per SIMD (<= 256 registers, 0 B scratch: 242 VGPRs); with 4-wave workgroups and 66 KB of LDS that is two workgroups per CU
-template <typename T, int NW>
+// CT: 1 = contracted coordinates (snerf_coords.contract of both levels; load_coords_ray).  Compile time: the run-time branch cost the bf16
+// kernel a spilled register.
+template <typename T, int NW, int CT = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void density_bwd_kernel(Args args) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
       p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
     } else {
       const uint32_t r = (uint32_t)nn / (uint32_t)a.c.S;  // N < 2^31 (checked by the launcher)
-      load_coords_ray(a.c, (int64_t)r, (int)((uint32_t)nn - r * (uint32_t)a.c.S), p);
+      load_coords_ray<6, CT>(a.c, (int64_t)r, (int)((uint32_t)nn - r * (uint32_t)a.c.S), p);
     }
     const float ga_g = a.gdens[nn];
     AxisTap tap[4];
@@ -487,11 +489,11 @@ static bool density_bwd_shape_ok(const snerf_kplanes_desc* d, const snerf_mlp_de
          (m->operands == 1 || m->operands == 2) && m->out_act == 0 && (m->hidden_act == 0 || m->hidden_act == 1);
 }
 
-template <typename T>
+template <typename T, int CT>
 static int launch_density_bwd(pbwd::Args& a, const int64_t* pairs, int n_levels, hipStream_t st) {
   constexpr int NW = 4;  // 8-wave workgroups (mlp_rows' shape) would need 121 KB of LDS: one per CU
   using P = pbwd::Plan<NW>;
-  auto k = pbwd::density_bwd_kernel<T, NW>;
+  auto k = pbwd::density_bwd_kernel<T, NW, CT>;
   SNERF_ALLOW_LDS(k, P::BYTES);
   // persistent grid sized to residency: as many workgroups as fit on the device at once, split between the levels by their pair counts
   static int resident = 0;
@@ -530,7 +532,7 @@ extern "C" int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, 
   SNERF_REQUIRE(levels && (n_levels == 1 || n_levels == 2), "kplanes_density_bwd: n_levels=%d (1 or 2)", n_levels);
   pbwd::Args a = {};
   int64_t pairs[2] = {0, 0};
-  int operands = 0, live = 0;
+  int operands = 0, live = 0, contract = -1;
   for (int l = 0; l < n_levels; ++l) {
     const snerf_density_bwd_level& L = levels[l];
     SNERF_REQUIRE(L.desc && L.coords && L.net, "kplanes_density_bwd: null descriptor (level %d)", l);
@@ -542,6 +544,9 @@ extern "C" int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, 
     SNERF_REQUIRE(L.N >= 0 && L.N < (1LL << 31), "kplanes_density_bwd: N=%lld (level %d)", (long long)L.N, l);
     SNERF_REQUIRE(L.coords->mode == 0 || (L.coords->mode == 1 && L.coords->S >= 1 && L.N % L.coords->S == 0), "kplanes_density_bwd: coords.mode=%d, N=%lld, S=%d",
                   L.coords->mode, (long long)L.N, L.coords->S);
+    SNERF_REQUIRE_CONTRACT(L.coords, "kplanes_density_bwd");
+    SNERF_REQUIRE(contract < 0 || L.coords->contract == contract, "kplanes_density_bwd: the levels' coords.contract differ (%d, %d)", contract, L.coords->contract);
+    contract = L.coords->contract;
     for (int k = 0; k < 4; ++k) SNERF_REQUIRE(L.desc->res[0][k] >= 1, "kplanes_density_bwd: res[0][%d]=%d", k, L.desc->res[0][k]);
     if (L.N == 0) continue;
     SNERF_REQUIRE(L.planes && L.W && L.gdens && L.grad_planes && L.workspace, "kplanes_density_bwd: null buffer (level %d)", l);
@@ -556,5 +561,7 @@ extern "C" int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, 
     ++live;
   }
   if (live == 0) return 0;
-  return operands == 2 ? launch_density_bwd<fp16>(a, pairs, live, (hipStream_t)stream) : launch_density_bwd<bf16>(a, pairs, live, (hipStream_t)stream);
+  if (contract == 1)
+    return operands == 2 ? launch_density_bwd<fp16, 1>(a, pairs, live, (hipStream_t)stream) : launch_density_bwd<bf16, 1>(a, pairs, live, (hipStream_t)stream);
+  return operands == 2 ? launch_density_bwd<fp16, 0>(a, pairs, live, (hipStream_t)stream) : launch_density_bwd<bf16, 0>(a, pairs, live, (hipStream_t)stream);
 }

@@ -168,6 +168,7 @@ extern "C" int snerf_kplanes_density_fwd(const snerf_kplanes_desc* desc, const f
                 net->n_hidden, net->d_out, net->operands);
   SNERF_REQUIRE(N >= 0 && N < (1LL << 31), "kplanes_density_fwd: N=%lld", (long long)N);
   SNERF_REQUIRE(coords->mode == 0 || coords->mode == 1, "kplanes_density_fwd: coords.mode=%d", coords->mode);
+  SNERF_REQUIRE_CONTRACT(coords, "kplanes_density_fwd");
   if (N == 0) return 0;
   SNERF_REQUIRE(coords->mode == 0 ? coords->pts != nullptr : (ray_coords_complete(coords, desc->n_coords) && coords->S > 0),
                 "kplanes_density_fwd: incomplete coordinates (times may be null only with three coordinates)");

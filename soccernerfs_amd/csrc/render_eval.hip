@@ -198,6 +198,7 @@ extern "C" int snerf_kplanes_field_render(const snerf_kplanes_desc* desc, const 
   FieldArgs a = {};
   a.d = *desc; a.planes = planes; a.c = *coords; a.N = (int64_t)R * coords->S; a.Wsig = W_sigma; a.Wcol = W_color;
   RayOut o = {transmittance_cutoff, rgb_out, acc_out, depth_median, depth_expected, median_index, samples_done};
+  if (coords->contract) return launch_field_render_contract(a, R, o, sigma->operands, (hipStream_t)stream, color->d_in != FF_GEO);
   if (desc->n_coords == 3) return launch_field_render_static(a, R, o, sigma->operands, (hipStream_t)stream, color->d_in != FF_GEO);
   FF_DISPATCH_FWD(launch_field_render, sigma->operands, desc->n_scales, a, R, o, (hipStream_t)stream, color->d_in != FF_GEO);
 }

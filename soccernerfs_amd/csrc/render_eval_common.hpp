@@ -47,7 +47,7 @@ __device__ __forceinline__ float tile_optical_depth(const float* dens, const flo
 
 // The render kernel (render_eval.hip describes it).  NP: planes per scale -- 6 is instantiated by render_eval.hip, 3 (a 3-coordinate descriptor) by
 // render_eval_static.hip.
-template <typename T, int NS, bool VD, int NP = 6>
+template <typename T, int NS, bool VD, int NP = 6, int CT = 0>
 __global__ __launch_bounds__(FF_NW * 64, 4) void field_render_kernel(FieldArgs a, int R, RayOut o) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(FF_NW * 64, 4) void field_render_kernel(FieldArgs a
     float tau = 0.f;
     int done = S;
     for (int t = 0; t < n_tiles; ++t) {
-      field_tile<T, NS, 0, VD, NP>(
+      field_tile<T, NS, 0, VD, NP, CT>(
           a, (int64_t)ray * S + t * FF_TS, smem, breg, [&](int row, int64_t, float v) { s_dd[t * FF_TS + row] = v; },
           [&](int row, int64_t, int c, float v) { s_col[(t * FF_TS + row) * 3 + c] = v; });
       if (o.cutoff > 0.f && t + 1 < n_tiles) {
@@ -91,5 +91,7 @@ inline int field_render_grid(int R) {
 
 // the render tail for a 3-coordinate descriptor (render_eval_static.hip)
 int launch_field_render_static(const FieldArgs& a, int R, const RayOut& o, int operands, hipStream_t st, bool vd);
+// the render tail with contracted coordinates (a.c.contract = 1), six or three planes (render_eval_contract.hip)
+int launch_field_render_contract(const FieldArgs& a, int R, const RayOut& o, int operands, hipStream_t st, bool vd);
 
 }  // namespace snerf

@@ -284,6 +284,7 @@ static int validate(const snerf_tgrid_desc* d, const snerf_coords* c, const floa
   SNERF_REQUIRE(B >= 0 && spr >= 1, "tgrid: B=%lld samples_per_row=%d", (long long)B, spr);
   SNERF_REQUIRE((trow != nullptr) != (times != nullptr), "tgrid: pass exactly one of temporal_row_index / times");
   SNERF_REQUIRE(c->mode == 0 || (c->mode == 1 && d->D == 3), "tgrid: coords.mode=%d with D=%d", c->mode, d->D);
+  SNERF_REQUIRE(c->contract == 0, "tgrid: coords.contract=%d: the table encoders have no scene contraction", c->contract);
   if (c->mode == 0) SNERF_REQUIRE(c->pts || B == 0, "tgrid: pts is null");
   if (c->mode == 1) SNERF_REQUIRE(c->S >= 1 && B % c->S == 0 && c->origins && c->dirs && c->ebins, "tgrid: bad ray coords");
   return 0;

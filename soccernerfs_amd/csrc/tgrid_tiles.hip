@@ -281,6 +281,7 @@ extern "C" int snerf_tgrid_bwd_bin(const snerf_tgrid_desc* desc, const snerf_tgr
   if (rc) return rc;
   SNERF_REQUIRE(coords && times && samples_per_row >= 1, "tgrid_bwd_bin: coords / times / samples_per_row");
   SNERF_REQUIRE(coords->mode == 0 || coords->mode == 1, "tgrid_bwd_bin: coords.mode=%d", coords->mode);
+  SNERF_REQUIRE(coords->contract == 0, "tgrid_bwd_bin: coords.contract=%d: the table encoders have no scene contraction", coords->contract);
   if (coords->mode == 0) SNERF_REQUIRE(coords->pts || B == 0, "tgrid_bwd_bin: pts is null");
   if (coords->mode == 1) SNERF_REQUIRE(coords->S >= 1 && B % coords->S == 0 && coords->origins && coords->dirs && coords->ebins, "tgrid_bwd_bin: bad ray coords");
   SNERF_REQUIRE(counts && tile_base && (pos4 || B == 0) && (records || plan->record_capacity == 0), "tgrid_bwd_bin: null buffer");

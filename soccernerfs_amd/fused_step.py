@@ -127,6 +127,7 @@ class FusedStep(FlatParams):
     self._fwd_rays (its ray count) and self._st, the HIP stream handle of the launches (set at the top of forward(); switched by _On)."""
 
     SPACING = 0  # snerf_spaced_bins / snerf_pdf_resample `kind`: 0 = uniform, 1 = UniformLinDispPiecewise (ray_samplers.py:242-243)
+    #              the default; a trainer sets it per instance (KPlanesTrainer: 1 with bounded = False, and its renderer follows)
     _timing, _timing_all = None, False
     _ck = staticmethod(_lib.check)  # every launch's return code goes through here (NerfplayerStep counts them)
 

@@ -29,6 +29,14 @@ def interpolate_kplanes(pts: torch.Tensor, ms_grids: PlaneSet, concat_features: 
     return ops.interpolate_kplanes(pts, ms_grids, freeze_time_planes, freeze_space_planes)
 
 
+def _contracts_in_kernel(spatial_distortion) -> bool:
+    """SceneContraction(order=inf) is what the gather kernels evaluate themselves (snerf_coords.contract); any other distortion stays
+    elementwise torch arithmetic in front of a gather of explicit points."""
+    from .spatial_distortions import SceneContraction
+
+    return type(spatial_distortion) is SceneContraction and spatial_distortion.order == float("inf")
+
+
 def _pts_from_positions(positions, times, aabb, rescale: bool, spatial_distortion=None):
     if spatial_distortion is not None:  # unbounded scene: contraction onto [-2, 2]^3, halved (kplanes_field.py:278-280, :438-440)
         p = spatial_distortion(positions) / 2.0
@@ -87,9 +95,11 @@ class KPlanesField(nn.Module):
 
     def _features(self, ray_samples: RaySamples):
         c = ray_samples._compact
-        if c is not None and c["times"] is not None and self.spatial_distortion is None:
+        contract = _contracts_in_kernel(self.spatial_distortion)
+        if c is not None and c["times"] is not None and (self.spatial_distortion is None or contract):
             return ops.interpolate_kplanes_rays(self.grids, c["origins"], c["directions"], c["times"], c["ebins"], self.aabb, rescale=True,
-                                                freeze_time_planes=self.freeze_time_planes, freeze_space_planes=self.freeze_space_planes)
+                                                freeze_time_planes=self.freeze_time_planes, freeze_space_planes=self.freeze_space_planes,
+                                                contract=contract)
         pts = _pts_from_positions(ray_samples.frustums.get_positions(), ray_samples.times, self.aabb, True, self.spatial_distortion)
         return ops.interpolate_kplanes(pts, self.grids, self.freeze_time_planes, self.freeze_space_planes)
 
@@ -147,12 +157,13 @@ class KPlanesDensityField(nn.Module):
         c = ray_samples._compact
         n_rays, n_samples = ray_samples.frustums.shape[:2]
         f = ops.interpolate_kplanes_rays(self.grids, c["origins"], c["directions"], c["times"], c["ebins"], self.aabb, rescale=False,
-                                         freeze_time_planes=self.freeze_time_planes, freeze_space_planes=self.freeze_space_planes)
+                                         freeze_time_planes=self.freeze_time_planes, freeze_space_planes=self.freeze_space_planes,
+                                         contract=_contracts_in_kernel(self.spatial_distortion))
         _, dens = self.sigma_net.forward_with_exp_head(f, 0)
         return dens.view(n_rays, n_samples, 1)
 
     def get_density(self, ray_samples: RaySamples):
-        if ray_samples._compact is not None and self.spatial_distortion is None:
+        if ray_samples._compact is not None and (self.spatial_distortion is None or _contracts_in_kernel(self.spatial_distortion)):
             return self.density_from_ray_samples(ray_samples), None
         return self.density_fn(ray_samples.frustums.get_positions(), ray_samples.times), None
 

@@ -46,13 +46,20 @@ def coords_from_points(pts: torch.Tensor) -> _lib.Coords:
     return c
 
 
-def coords_from_rays(origins, dirs, times, ebins, aabb, rescale: bool) -> _lib.Coords:
+def coords_from_rays(origins, dirs, times, ebins, aabb, rescale: bool, contract: bool = False) -> _lib.Coords:
+    """contract: the L-inf scene contraction and the fields' halving in place of the box normalisation (snerf_coords.contract; unbounded
+    scenes).  aabb and rescale are then not read by any kernel; aabb may be None."""
     c = _lib.Coords()
     c.mode = 1
     c.S = ebins.shape[-1] - 1
     c.rescale = int(rescale)
+    c.contract = int(bool(contract))
     c.origins, c.dirs, c.ebins = origins.data_ptr(), dirs.data_ptr(), ebins.data_ptr()
     c.times = times.data_ptr() if times is not None else None  # None: a static scene (3-coordinate descriptors never read it)
+    if aabb is None:
+        if not contract:
+            raise ValueError("coords_from_rays: aabb is None (only contracted coordinates do without the scene box)")
+        return c
     a = aabb_host(aabb)
     for k in range(3):
         c.aabb_min[k] = a[0][k]
@@ -249,12 +256,13 @@ def interpolate_kplanes(pts: torch.Tensor, plane_set: PlaneSet, freeze_time_plan
 
 
 def interpolate_kplanes_rays(plane_set: PlaneSet, origins, dirs, times, ebins, aabb, rescale: bool, freeze_time_planes: bool = False,
-                             freeze_space_planes: bool = False) -> torch.Tensor:
-    """Same gather with sample coordinates derived in-kernel from rays + euclidean bin edges [R,S+1]."""
+                             freeze_space_planes: bool = False, contract: bool = False) -> torch.Tensor:
+    """Same gather with sample coordinates derived in-kernel from rays + euclidean bin edges [R,S+1].  contract: SceneContraction(order=inf)
+    and the halving in-kernel instead of the box normalisation (coords_from_rays)."""
     origins, dirs, ebins = _f32c(origins, "origins"), _f32c(dirs, "dirs"), _f32c(ebins, "ebins")
     times = _f32c(times, "times").reshape(-1)
     R, S = ebins.shape[0], ebins.shape[1] - 1
-    c = coords_from_rays(origins, dirs, times, ebins, aabb, rescale)
+    c = coords_from_rays(origins, dirs, times, ebins, aabb, rescale, contract)
     freeze = int(bool(freeze_time_planes)) | (int(bool(freeze_space_planes)) << 1)
     return _KPlanesGather.apply(plane_set.planes, plane_set, (origins, dirs, times, ebins), c, R * S, freeze, None)
 
@@ -809,7 +817,7 @@ CAMERA_TYPES = (1, 2, 3)  # CameraType of NS/cameras/cameras.py:42-47: perspecti
 
 
 def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_plane: float = 0.0, training: bool = True, distortion_params=None,
-                  camera_type=None, validate_camera_type: bool = True):
+                  camera_type=None, validate_camera_type: bool = True, collider: str = "aabb", far_plane: Optional[float] = None):
     """RayGenerator.forward (+ AABBBoxCollider when aabb is given).  indices int64 [R,3]; per-camera fx,fy,cx,cy [M],
     c2w [M,3,4], cam_times [M].  Returns dict of origins, directions, pixel_area, directions_norm, times, (nears, fars).
     distortion_params: None = pinhole rays (snerf_raygen); a float32 tensor [M,6] (one OpenCV row k1 k2 k3 k4 p1 p2 per camera) or [6] (one row
@@ -817,7 +825,16 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
     camera_type: None = all perspective (the two entries above, as ever); an int or a CameraType (one type for all cameras) or an integer tensor
     [M] (one per camera, mixed tables included) = snerf_raygen_cam (cameras.py:663-700: 1 perspective, 2 fisheye, 3 equirectangular, which ignores
     the lens rows).  A value outside 1..3 raises, as the reference does; for a device tensor that check reads it back, so a caller that has
-    checked its table on the host (Cameras does, once, in its constructor) passes validate_camera_type=False."""
+    checked its table on the host (Cameras does, once, in its constructor) passes validate_camera_type=False.
+    collider: "aabb" (default) = the box collider inside the ray kernel when aabb is given; "near_far" = NearFarCollider
+    (scene_colliders.py:170-188; unbounded scenes): the ray kernel runs without a collider and nears / fars are the constants near_plane (in
+    training; 0 otherwise) and far_plane, which must be given; aabb is ignored."""
+    if collider not in ("aabb", "near_far"):
+        raise ValueError(f"generate_rays: collider={collider!r} (\"aabb\" or \"near_far\")")
+    if collider == "near_far":
+        if far_plane is None:
+            raise ValueError("generate_rays: collider=\"near_far\" needs far_plane")
+        aabb = None
     if not indices.is_cuda or indices.dtype != torch.int64:
         raise RuntimeError("generate_rays: indices must be an int64 HIP device tensor")
     indices = indices.contiguous()
@@ -868,6 +885,9 @@ def generate_rays(indices, fx, fy, cx, cy, c2w, cam_times=None, aabb=None, near_
         _lib.call("raygen_lens", C.byref(a), _stream())
     else:
         _lib.call("raygen", C.byref(a), _stream())
+    if collider == "near_far":
+        out["nears"] = torch.full((R, 1), float(near_plane) if training else 0.0, dtype=torch.float32, device=dev)
+        out["fars"] = torch.full((R, 1), float(far_plane), dtype=torch.float32, device=dev)
     out["camera_indices"] = indices[:, 0:1]
     return out
 

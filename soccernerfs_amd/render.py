@@ -63,6 +63,8 @@ class KPlanesRenderer:
             raise ValueError(f"transmittance_cutoff={transmittance_cutoff}: expected 0 <= cutoff < 1")
         self.trainer, self.R, self.dev = trainer, int(rays_per_chunk), trainer.dev
         self.cfg, self.S, self.aabb, self.lib = trainer.cfg, trainer.S, trainer.aabb, trainer.lib
+        # an unbounded trainer (cfg.bounded = False): contracted coordinates, the piecewise spacing and NearFarCollider in eval mode (near 0)
+        self.contract, self.SPACING = bool(getattr(trainer, "contract", False)), trainer.SPACING
         self.transmittance_cutoff = float(transmittance_cutoff)
         S2 = self.S[2]
         # a cutoff asks for the fused tail: only that kernel knows a ray's transmittance before its last sample is decoded
@@ -75,6 +77,11 @@ class KPlanesRenderer:
         self.buf = {"sb": [f(R, s + 1) for s in self.S], "eb": [f(R, s + 1) for s in self.S],
                     "dens": [f(R, self.S[0]), f(R, self.S[1]), None], "w": [f(R, self.S[0]), f(R, self.S[1]), None]}
         self._rays = {"origins": f(R, 3), "directions": f(R, 3), "pixel_area": f(R), "directions_norm": f(R), "times": f(R), "nears": f(R), "fars": f(R)}
+        if self.contract:
+            # the frame ray kernels always write their box interval: it goes to a side buffer nobody reads, and the samplers see the constants
+            self._box_interval = (self._rays["nears"], self._rays["fars"])
+            self._rays["nears"] = torch.zeros(R, dtype=torch.float32, device=self.dev)
+            self._rays["fars"] = torch.full((R,), float(self.cfg.far_plane), dtype=torch.float32, device=self.dev)
         if not self.fused_tail:
             self.buf["dens"][2], self.buf["w"][2], self.buf["rgb"] = f(R, S2), f(R, S2), f(R * S2, 3)
             if not trainer.fused_field:
@@ -131,7 +138,7 @@ class KPlanesRenderer:
         self._spaced_bins(None)
         o, d, t = rays["origins"], rays["directions"], rays["times"]
         for lvl in range(2):
-            co = ops.coords_from_rays(o, d, t, b["eb"][lvl], self.aabb, False)
+            co = ops.coords_from_rays(o, d, t, b["eb"][lvl], self.aabb, False, self.contract)
             N, net = n * self.S[lvl], tr.prop_nets[lvl]
             if tr.fused_proposal:
                 with self._span("kplanes_density_fwd"):
@@ -144,7 +151,7 @@ class KPlanesRenderer:
                 self._mlp_fwd(net, b["pfeat"][lvl], self.cfg.proposal_feature_dim, N, b["pout"][lvl], 1, 0, b["dens"][lvl])
             self._resample(lvl, None, anneal)
         S2 = self.S[2]
-        co = ops.coords_from_rays(o, d, t, b["eb"][2], self.aabb, True)
+        co = ops.coords_from_rays(o, d, t, b["eb"][2], self.aabb, True, self.contract)
         rgb, acc, depth = out["rgb"][p0:p1], out["accumulation"][p0:p1], out["depth"][p0:p1]
         if self.fused_tail:
             sd = self.samples_done[p0:p1] if self.samples_done is not None else None
@@ -164,7 +171,7 @@ class KPlanesRenderer:
             for r0 in range(0, n, self._FIELD_SLICE):
                 r1 = min(r0 + self._FIELD_SLICE, n)
                 N = (r1 - r0) * S2
-                cs = ops.coords_from_rays(o[r0:r1], d[r0:r1], t[r0:r1], b["eb"][2][r0:r1], self.aabb, True)
+                cs = ops.coords_from_rays(o[r0:r1], d[r0:r1], t[r0:r1], b["eb"][2][r0:r1], self.aabb, True, self.contract)
                 with self._span("kplanes_gather_fwd.field"):
                     self._call("kplanes_gather_fwd", C.byref(tr._desc_field), self._p(tr.field_planes.planes), C.byref(cs), N, self._p(b["feat"]),
                                self._st)
@@ -219,7 +226,8 @@ class KPlanesRenderer:
             ra.aabb_min[k], ra.aabb_max[k] = self.aabb[0][k], self.aabb[1][k]
         rays = self._rays
         ra.origins, ra.dirs, ra.pixel_area, ra.dir_norm = (rays[k].data_ptr() for k in ("origins", "directions", "pixel_area", "directions_norm"))
-        ra.times, ra.nears, ra.fars = rays["times"].data_ptr(), rays["nears"].data_ptr(), rays["fars"].data_ptr()
+        box_near, box_far = self._box_interval if self.contract else (rays["nears"], rays["fars"])
+        ra.times, ra.nears, ra.fars = rays["times"].data_ptr(), box_near.data_ptr(), box_far.data_ptr()
         f = lambda c: torch.empty(H * W, c, dtype=torch.float32, device=self.dev)
         out = {"rgb": f(3), "accumulation": f(1), "depth": f(1)}
         self.samples_done = torch.empty(H * W, dtype=torch.int32, device=self.dev) if self.record_samples_done and self.fused_tail else None

@@ -80,17 +80,53 @@ def _cell_hash(ix: torch.Tensor, iy: torch.Tensor, salt: int) -> torch.Tensor:
     return ((h ^ (h >> 16)) & 0xFFFF).float() / 65536.0
 
 
-def shade(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, variant: str = "default", dynamic: bool = True) -> torch.Tensor:
+BACKDROP_RADIUS = 6.0  # the far stand: a ring of seats four scene radii out (the pitch scene ends at |x|, |y| < 1.45)
+
+
+def _backdrop(o: torch.Tensor, d: torch.Tensor, sky: torch.Tensor) -> torch.Tensor:
+    """What a ray sees where it leaves the pitch scene (shade(backdrop=True); unbounded-scene studies): a stronger sky gradient, bare ground
+    out to the stand, and the stand -- the cylinder x^2 + y^2 = BACKDROP_RADIUS^2 for z in [-0.1, 1.4], 4 cm seat cells of hashed colour,
+    darker towards the top.  Nothing of it lies inside any usable scene box: only a contracted model can represent it."""
+    up = d[:, 2].clamp(-1, 1)
+    col = torch.stack([0.35 + 0.45 * (1 - up.abs()), 0.55 + 0.3 * (1 - up.abs()), 0.9 + 0.05 * up], -1).clamp(0, 1) * 0.5 + sky * 0.5
+    # the cylinder: |o_xy + t d_xy| = R, the far root
+    a = (d[:, :2] ** 2).sum(-1).clamp(min=1e-9)
+    b = (o[:, :2] * d[:, :2]).sum(-1)
+    c = (o[:, :2] ** 2).sum(-1) - BACKDROP_RADIUS ** 2
+    disc = b * b - a * c
+    tc = (-b + torch.sqrt(disc.clamp(min=0))) / a
+    pc = o + d * tc.clamp(min=0, max=1e4)[:, None]
+    stand = (disc > 0) & (tc > 0) & (pc[:, 2] > -0.1) & (pc[:, 2] < 1.4)
+    ang = torch.atan2(pc[:, 1], pc[:, 0])
+    seats = torch.stack([_cell_hash((ang * BACKDROP_RADIUS * 25).floor(), (pc[:, 2].clamp(-1, 2) * 25).floor(), 51 + k) for k in range(3)], -1) * 0.6 + 0.2
+    seats = seats * (1.0 - 0.4 * ((pc[:, 2] + 0.1) / 1.5).clamp(0, 1))[:, None]
+    # bare ground between the pitch and the stand
+    tz = (-0.1 - o[:, 2]) / torch.where(d[:, 2].abs() < 1e-6, torch.full_like(d[:, 2], -1e-6), d[:, 2])
+    pg = o + d * tz.clamp(min=0, max=1e4)[:, None]
+    ground = (tz > 0) & ((pg[:, :2] ** 2).sum(-1) < BACKDROP_RADIUS ** 2)
+    rings = ((pg[:, :2] ** 2).sum(-1).sqrt() * 2).floor() % 2
+    earth = torch.stack([0.42 + 0.05 * rings, 0.36 + 0.04 * rings, 0.28 + 0.02 * rings], -1)
+    col = torch.where(stand[:, None], seats, col)
+    return torch.where(ground[:, None], earth, col)
+
+
+def shade(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, variant: str = "default", dynamic: bool = True, backdrop: bool = False) -> torch.Tensor:
     """Analytic colour in [0,1] for rays (o,d [N,3], unit d) at times [N].  variant "textured" (round 4; PSNR studies on content that does
     not saturate): the same pitch with fine grass / wear texture on it, an advertising board and a crowd stand behind the far touchline,
     and ten players instead of three.  dynamic=False leaves out players and ball: the empty scene the reference's dataparsers read from their
-    "empty" directory for static pre-training (broadcaststyle_dataparser.py `static`); the result does not depend on time."""
+    "empty" directory for static pre-training (broadcaststyle_dataparser.py `static`); the result does not depend on time.
+    backdrop=True (opt-in; "default" and "textured"): where a ray leaves the pitch scene it sees _backdrop -- a sky gradient, bare ground and a
+    far stand at several scene radii -- instead of the plain sky; the default scenes keep their bits."""
     if variant == "stadium":
+        if backdrop:
+            raise ValueError("backdrop is built for the default and the textured scene")
         return shade_stadium(o, d, time, dynamic)
     textured = variant == "textured"
     assert variant in ("default", "textured")
     N = o.shape[0]
     sky = torch.stack([0.55 + 0.2 * d[:, 2], 0.7 + 0.15 * d[:, 2], 0.95 * torch.ones_like(d[:, 2])], -1).clamp(0, 1)
+    if backdrop:
+        sky = _backdrop(o, d, sky)
     # ground plane z = -0.1: mown-stripe pitch + lines
     tz = (-0.1 - o[:, 2]) / torch.where(d[:, 2].abs() < 1e-6, torch.full_like(d[:, 2], -1e-6), d[:, 2])
     tg = torch.where(tz > 0, tz, torch.full_like(tz, float("inf")))
@@ -265,14 +301,14 @@ def shade_stadium(o: torch.Tensor, d: torch.Tensor, time: torch.Tensor, dynamic:
 
 
 def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, device, chunk_rows: int = 135, variant: str = "default",
-                   dynamic: bool = True) -> Dict[str, torch.Tensor]:
+                   dynamic: bool = True, backdrop: bool = False) -> Dict[str, torch.Tensor]:
     """uint8 images [M,H,W,3] on `device` for every (camera in cam_ids) x (time), plus per-image camera tables
     (one 'camera' per image, as nerfstudio's Cameras object holds them: c2w/intrinsics repeated per frame + times).
     cams may carry "distortion": OpenCV rows k1 k2 k3 k4 p1 p2, [n_cams,6] or [6] for all cameras.  The dataset is then shot through that lens
     (ops.generate_rays(distortion_params=...)) and the returned table carries "distortion" [M,6]; without the entry nothing changes.
     cams may carry "camera_type": an int or CameraType for all cameras, or one per camera [n_cams] (1 perspective, 2 fisheye, 3 equirectangular).
     The dataset is then shot with cameras of those types (ops.generate_rays(camera_type=...)) and the returned table carries "camera_type"
-    int32 [M]; without the entry nothing changes.  dynamic=False: the empty scene (shade)."""
+    int32 [M]; without the entry nothing changes.  dynamic=False: the empty scene (shade).  backdrop=True: shade's far backdrop."""
     from . import ops
 
     H, W = cams["height"], cams["width"]
@@ -312,7 +348,7 @@ def render_dataset(cams: Dict[str, torch.Tensor], times: torch.Tensor, cam_ids, 
             idx = torch.stack([torch.full_like(yy, m), yy, xx], -1).reshape(-1, 3)
             rays = ops.generate_rays(idx, table["fx"], table["fy"], table["cx"], table["cy"], table["c2w"], table["times"],
                                      distortion_params=table.get("distortion"), camera_type=table.get("camera_type"), validate_camera_type=False)
-            col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant, dynamic)
+            col = shade(rays["origins"], rays["directions"], rays["times"][:, 0], variant, dynamic, backdrop)
             imgs[m, r0:r0 + rows.numel()] = (col.view(rows.numel(), W, 3) * 255.0 + 0.5).to(torch.uint8)
     return {"images": imgs, **table, "width": W, "height": H}
 

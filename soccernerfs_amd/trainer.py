@@ -42,6 +42,12 @@ class KPlanesTrainConfig:
     num_nerf_samples_per_ray: int = 64
     use_single_jitter: bool = False
     near_plane: float = 0.0  # AABBBoxCollider default (kplanes.py:276-277)
+    # KPlanesModelConfig.bounded (NS/models/kplanes.py:77-78, 194, 260-281).  False = an unbounded scene: SceneContraction(order=inf) in all three
+    # fields (evaluated inside the kernels: snerf_coords.contract), NearFarCollider(near_plane, far_plane) in place of the box
+    # collider and the UniformLinDispPiecewise spacing for the first level and both resamples.  near_plane keeps this config's default of 0.0; the
+    # reference MODEL's default is 0.05, and NearFarCollider applies it in training only (0 at evaluation).  aabb_scale is then not read.
+    bounded: bool = True
+    far_plane: float = 1000.0
     proposal_warmup: int = 5000
     proposal_update_every: int = 5
     proposal_weights_anneal_max_num_iters: int = 1000
@@ -202,7 +208,8 @@ class KPlanesTrainer(FusedStep):
         if cfg.ray_gradients:
             # what the ray gradient does not cover raises here, by name and before anything is allocated, instead of training the poses on a
             # partial gradient.  (The depth losses are switched on per step, by handing backward() / train_step() termination depths: refused
-            # there.  This trainer has no scene contraction, no linear decoder and no chunked backward to refuse.)
+            # there.  Scene contraction (bounded = False) is covered: snerf_kplanes_gather_bwd_coords carries the contraction's Jacobian.  This trainer
+            # has no linear decoder and no chunked backward to refuse.)
             if not cfg.disable_viewing_dependent:
                 raise NotImplementedError("ray_gradients with disable_viewing_dependent=False is not built: the SH branch's gradient w.r.t. the ray direction")
             if self.world > 1:
@@ -235,6 +242,15 @@ class KPlanesTrainer(FusedStep):
         gen = torch.Generator().manual_seed(cfg.seed)
         a = cfg.aabb_scale
         self.aabb = [[-a, -a, -a], [a, a, a]]
+        # unbounded scene: contracted coordinates at all three levels, piecewise spacing (an instance attribute: FusedStep.SPACING is the bounded
+        # default), and constant nears / fars per mode, filled once here -- a step gains no launch
+        self.contract = not cfg.bounded
+        self.SPACING = 0 if cfg.bounded else 1
+        if self.contract:
+            if not (cfg.near_plane >= 0.0 and cfg.far_plane > cfg.near_plane):
+                raise ValueError(f"bounded=False needs far_plane > near_plane >= 0; got near_plane={cfg.near_plane} far_plane={cfg.far_plane}")
+            full = lambda v: torch.full((num_rays, 1), float(v), dtype=torch.float32, device=self.dev)
+            self._near_far = {True: (full(cfg.near_plane), full(cfg.far_plane)), False: (full(0.0), full(cfg.far_plane))}
         base = list(cfg.spacetime_resolution)
         reso = [[r * m for r in base[:3]] + base[3:] for m in cfg.multiscale_res]
         def mlp(din, dout, h, nh, act, operands):
@@ -531,7 +547,9 @@ class KPlanesTrainer(FusedStep):
         if self.field_fwd_time_order:  # first on the main stream: done long before the field forward, under the previous step's sweep
             with self._span("ray_time_order"):
                 self._call("ray_time_order", self._p(t), R, self._p(self._ray_order), self._st)
-        if "nears" not in rays:
+        if "nears" not in rays and self.contract:  # NearFarCollider: near_plane in training, 0 otherwise
+            rays["nears"], rays["fars"] = (t_[:R] for t_ in self._near_far[bool(training)])
+        elif "nears" not in rays:
             rays["nears"], rays["fars"] = ops.aabb_collide(o, d, self.aabb, cfg.near_plane, training)
         else:
             rays["nears"], rays["fars"] = ops._f32c(rays["nears"], "rays['nears']"), ops._f32c(rays["fars"], "rays['fars']")
@@ -540,7 +558,7 @@ class KPlanesTrainer(FusedStep):
         self._coords = []
         for lvl in range(3):
             rescale = lvl == 2  # proposal fields keep [0,1] coordinates (kplanes_field.py:440), the main field maps to [-1,1] (:283-284)
-            co = ops.coords_from_rays(o, d, t, b["eb"][lvl], self.aabb, rescale)
+            co = ops.coords_from_rays(o, d, t, b["eb"][lvl], self.aabb, rescale, self.contract)
             self._coords.append(co)
             N = R * self.S[lvl]
             if lvl < 2 and self.fused_proposal:
@@ -676,7 +694,7 @@ class KPlanesTrainer(FusedStep):
                           sl(b["gfeat"]), F, x16=self._fwd_fused)
         rays = self.rays
         times = rays["times"].reshape(-1)[r0:r1] if rays["times"] is not None else None
-        co = ops.coords_from_rays(rays["origins"][r0:r1], rays["directions"][r0:r1], times, b["eb"][2][r0:r1], self.aabb, True)
+        co = ops.coords_from_rays(rays["origins"][r0:r1], rays["directions"][r0:r1], times, b["eb"][2][r0:r1], self.aabb, True, self.contract)
         if self.sorted_scatter and self.grads_fx is None and self._sort_done is not None and r0 == 0 and r1 == self.R:
             torch.cuda.current_stream().wait_event(self._sort_done)
             ss = self._ss

@@ -38,7 +38,7 @@ def config_from_overrides(pairs) -> KPlanesTrainConfig:
     return KPlanesTrainConfig(**kw)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--load-dir", required=True, help="directory holding step-*.ckpt (nerfstudio checkpoint format)")
     ap.add_argument("--load-step", type=int, default=None, help="checkpoint step (default: the newest)")
@@ -53,9 +53,25 @@ def main(argv=None):
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="KPlanesTrainConfig override, repeatable")
     ap.add_argument("--freeze-time-planes", action="store_true", help="the checkpoint is a static pre-training stage (KPlanesTrainConfig.freeze_time_planes): "
                     "render from the space planes alone; the path needs no render_time and --default-time is ignored")
+    ap.add_argument("--unbounded", action="store_true", help="the checkpoint is an unbounded scene (KPlanesTrainConfig.bounded=False): contracted "
+                    "coordinates, near / far collider (near 0 at evaluation) and piecewise spacing; the checkpoint does not record this")
+    ap.add_argument("--far-plane", type=float, default=None, help="with --unbounded: the far plane the model was trained with (default: the config's 1000)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
-    cfg = config_from_overrides(args.set + (["freeze_time_planes=True"] if args.freeze_time_planes else []))
+    if args.far_plane is not None and not args.unbounded:
+        ap.error("--far-plane needs --unbounded")
+    return args
+
+
+def config_from_args(args) -> KPlanesTrainConfig:
+    """The trainer configuration a command line stands for: --set pairs, then the switches that name a config field of their own."""
+    unbounded = (["bounded=False"] + ([f"far_plane={args.far_plane}"] if args.far_plane is not None else [])) if args.unbounded else []
+    return config_from_overrides(args.set + (["freeze_time_planes=True"] if args.freeze_time_planes else []) + unbounded)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cfg = config_from_args(args)
     trainer = KPlanesTrainer(cfg, 4096, args.device)
     step = trainer.load_checkpoint(args.load_dir, args.load_step)
     renderer = KPlanesRenderer(trainer, rays_per_chunk=args.eval_num_rays_per_chunk, transmittance_cutoff=args.transmittance_cutoff,

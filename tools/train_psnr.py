@@ -31,6 +31,11 @@ from soccernerfs_amd.pixel_samplers import DynamicBasedPixelSampler, compute_ist
 from soccernerfs_amd.trainer import KPlanesTrainConfig, KPlanesTrainer, anneal_value  # noqa: E402
 
 
+def collider_args(cfg) -> dict:
+    """ops.generate_rays' collider for a trainer config: the box (default), or near / far constants for an unbounded scene."""
+    return {} if getattr(cfg, "bounded", True) else {"collider": "near_far", "far_plane": cfg.far_plane}
+
+
 @torch.no_grad()
 def eval_set(trainer, data, image_ids, anneal, with_ssim=True):
     """PSNR (and SSIM) of full-image renders of data["images"][image_ids]."""
@@ -44,7 +49,8 @@ def eval_set(trainer, data, image_ids, anneal, with_ssim=True):
         out = torch.empty(H * W, 3, device=imgs.device)
         for i in range(0, H * W, R):
             rays = ops.generate_rays(idx[i:i + R].contiguous(), data["fx"], data["fy"], data["cx"], data["cy"], data["c2w"], data["times"],
-                                     aabb=trainer.aabb, near_plane=trainer.cfg.near_plane, training=False, distortion_params=data.get("ray_distortion"))
+                                     aabb=trainer.aabb, near_plane=trainer.cfg.near_plane, training=False, distortion_params=data.get("ray_distortion"),
+                                     **collider_args(trainer.cfg))
             out[i:i + R] = trainer.forward(rays, None, anneal, training=False)
         gt = imgs[m].reshape(-1, 3).float() / 255.0
         mse = torch.mean((out - gt) ** 2)
@@ -114,7 +120,7 @@ def static_pretrain(args, cfg, trainer, train, R, dev):
     for _ in range(args.static_pretrain):
         idx, target = ops.sample_pixels_uniform(torch.rand(R, 3, device=dev), M, H, W, images=empty["images"])
         rays = ops.generate_rays(idx, empty["fx"], empty["fy"], empty["cx"], empty["cy"], empty["c2w"], empty["times"], aabb=stage1.aabb,
-                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"))
+                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"), **collider_args(cfg))
         stage1.train_step(rays, target)
     with tempfile.TemporaryDirectory() as d:
         stage1.save_checkpoint(d)
@@ -132,6 +138,8 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
                              emulate_transports=args.emulate_transports, quotient_epilogue=not args.no_quotient_epilogue, fused_proposal=not args.no_fused_proposal,
                              sigma_operands=args.sigma_operands, color_operands=args.color_operands, proposal_operands=args.proposal_operands,
                              ray_gradients=args.optimize_cameras)
+    if args.unbounded:  # contracted coordinates, near / far collider, piecewise spacing (KPlanesTrainConfig.bounded)
+        cfg.bounded, cfg.near_plane, cfg.far_plane = False, args.near_plane, args.far_plane
     if args.static_scene:  # the original static K-Planes model: three planes per scale, no time axis (kplanes_field.py:59-61)
         cfg.spacetime_resolution = tuple(cfg.spacetime_resolution)[:3]
         cfg.proposal_resolutions = tuple(tuple(r)[:3] for r in cfg.proposal_resolutions)
@@ -214,7 +222,7 @@ def run_one(args, seed, train, sets, ist, dev, log_steps=True):
         target = train["images"][idx[:, 0], idx[:, 1], idx[:, 2]].float() / 255.0
         table = cam_opt.adjusted_camera_to_worlds(cameras) if cam_opt is not None else train["c2w"]
         rays = ops.generate_rays(idx, train["fx"], train["fy"], train["cx"], train["cy"], table, train["times"], aabb=trainer.aabb,
-                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"))
+                                 near_plane=cfg.near_plane, training=True, distortion_params=train.get("ray_distortion"), **collider_args(cfg))
         trainer.train_step(rays, target)
         if cam_opt is not None:
             cam_opt.backward(idx, trainer.ray_grads)
@@ -287,6 +295,12 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="single-stream step (A/B against stream-ordering effects)")
     ap.add_argument("--static-pretrain", type=int, default=0, metavar="N", help="N steps with freeze_time_planes on the empty scene (no players, no ball) first, "
                     "then the usual run from those planes (KPlanesTrainer.load_checkpoint(params_only=True)); compare against --steps raised by N")
+    ap.add_argument("--unbounded", action="store_true", help="KPlanesTrainConfig.bounded=False: L-inf scene contraction in the kernels, near / far collider, "
+                    "piecewise spacing (DESIGN.md 4.15); compare with --backdrop, whose far content no scene box holds")
+    ap.add_argument("--near-plane", type=float, default=0.05, help="with --unbounded: the collider's near plane in training (the reference model's default)")
+    ap.add_argument("--far-plane", type=float, default=1000.0, help="with --unbounded: the collider's far plane")
+    ap.add_argument("--backdrop", action="store_true", help="synthetic.shade(backdrop=True): a sky gradient, bare ground and a far stand at several scene "
+                    "radii where a ray leaves the pitch scene")
     ap.add_argument("--static-scene", action="store_true", help="a 3-coordinate model (three planes per scale, no time axis) on the empty scene")
     # a value such as -0.25,0.08,... starts with '-' and is no plain number, so argparse would read it as an option: hand it over as --lens=VALUE
     argv = sys.argv[1:]
@@ -314,6 +328,8 @@ def main():
         ap.error("--share-poses-per-camera needs --optimize-cameras")
     if args.optimize_cameras and (args.standin or args.view_dependent):
         ap.error("--optimize-cameras runs on the HIP trainer with disable_viewing_dependent=True")
+    if args.unbounded and args.standin:
+        ap.error("--unbounded runs on the HIP trainer (the stock-PyTorch stand-in is the bounded model)")
     if args.use_masks and not args.overlay:
         ap.error("--use-masks needs --overlay")
     if args.mask_ist and not args.use_masks:
@@ -334,11 +350,11 @@ def main():
         ap.error("--ignore-lens needs --lens")
     times = synthetic.frame_times(100, 3)
     dyn = not args.static_scene
-    train = synthetic.render_dataset(cams, times, list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
-    held = synthetic.render_dataset(cams, times, [19], dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
-    novel = synthetic.render_dataset(novel_cams, times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene, dynamic=dyn)
+    train = synthetic.render_dataset(cams, times, list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=dyn, backdrop=args.backdrop)
+    held = synthetic.render_dataset(cams, times, [19], dev, chunk_rows=540, variant=args.scene, dynamic=dyn, backdrop=args.backdrop)
+    novel = synthetic.render_dataset(novel_cams, times, [0, 1, 2], dev, chunk_rows=540, variant=args.scene, dynamic=dyn, backdrop=args.backdrop)
     if args.static_pretrain:  # the reference's "empty" directory: the training cameras' view of the scene without players and ball
-        train["empty"] = synthetic.render_dataset(cams, times[:1], list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=False)
+        train["empty"] = synthetic.render_dataset(cams, times[:1], list(range(19)), dev, chunk_rows=540, variant=args.scene, dynamic=False, backdrop=args.backdrop)
     if args.overlay:
         box = [int(v) for v in args.overlay.split(",")]
         if len(box) != 4:

@@ -402,6 +402,13 @@ typedef struct {
 } snerf_density_bwd_level;
 int snerf_kplanes_density_bwd_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* net);
 int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, int32_t n_levels, snerf_stream_t stream);
+/* Added to ABI 16 revision 2's surface (see SNERF_ABI_REVISION): the same launch under a RESIDENCY BUDGET.  The kernel's grid is persistent -- as
+ * many workgroups as the device holds at once, each with its own range of 32-sample pairs -- and two of its workgroups fill a CU's registers, so
+ * a kernel on another stream starts no wave until the launch ends.  max_workgroups caps the grid: grid = min(needed, resident,
+ * max(max_workgroups, live levels)), each workgroup then owns a longer range and the rest of the device stays free for the other stream.
+ * max_workgroups <= 0: no cap (snerf_kplanes_density_bwd forwards with 0).  Results: gX bit-identical for every budget; plane and weight
+ * gradients the same terms, grouped along the longer ranges. */
+int snerf_kplanes_density_bwd_budget(const snerf_density_bwd_level* levels, int32_t n_levels, int32_t max_workgroups, snerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Compositing and ray-level losses (one wavefront per ray, S <= 320).

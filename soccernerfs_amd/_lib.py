@@ -222,6 +222,7 @@ SIGNATURES = {
     "snerf_kplanes_density_fwd": "s:PPPLPPPPP",
     "snerf_kplanes_density_bwd_supported": "i:PP",
     "snerf_kplanes_density_bwd": "s:PIP",
+    "snerf_kplanes_density_bwd_budget": "s:PIIP",
     "snerf_render_fwd": "s:PP",
     "snerf_ray_train_fwd_bwd": "s:PP",
     "snerf_render_bwd": "s:PPPIPPIIPPIP",

@@ -37,13 +37,24 @@ constexpr int C = 8, K0P = 16, H = 64, HB = H / 16, HK = H / 32, NPL = 6;
 // LDS plan in 16-bit elements: mlp_rows' PlanR<16,64,1> (weights, then one [32][80] + [32][16] image pair per wave), then per wave the
 // walk's taps ([32 samples][4 axes] x {i0, i1, w0, w1}, 2 KB) and the per-plane values v_q ([32][6][8] fp32, 6 KB: kept out of the registers
 // across the net).  The per-plane gradient factors reuse the wave's image pair (6 KB) once the weight-gradient products are done.
+//
+// The output layer has ONE output, so of mlp_rows' two 16-wide images of it only output 0 is stored: WOT keeps row 0 and WOR column block 0
+// ([H][4]: outputs 0..3).  Every lane reads the stored part and the lanes of the other outputs (1..15 of WOT's rows, 4..15 of WOR's columns)
+// replace what they read by the zeros those images held there, so the MFMA operands keep their values.  That is 4 208 B less (62 864 B), which
+// is what lets one workgroup of this kernel and three of the field scatter's pass B (scatter_halfwave_kernel's s_rec, PASS_B_LDS each) share a
+// CU: see the assert below and the launcher's budget.
+// gfx950: 160 KB per CU.  The allocation step is taken as 320 dwords, the compiler's LDS granularity for this target and the coarser reading: in
+// 128-dword steps the sum asserted below is 2 KB smaller.
+constexpr int LDS_PER_CU = 160 * 1024, LDS_GRANULE = 1280, PASS_B_LDS = 32 * 1024;
+constexpr size_t lds_alloc(size_t bytes) { return (bytes + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE; }
+
 template <int NW>
 struct Plan {
-  static constexpr int L0 = K0P + 4, LH = H + 8, LO = 16 + 4;
+  static constexpr int L0 = K0P + 4, LH = H + 8, LO = 4;
   static constexpr int W0T = 0;               // [H][L0]    forward layer 0: natural k (features)
   static constexpr int W0R = W0T + H * L0;    // [K0P][LH]  gX: k = hidden units, permuted
-  static constexpr int WOT = W0R + K0P * LH;  // [16][LH]   output layer: row = output, k = hidden units, permuted
-  static constexpr int WOR = WOT + 16 * LH;   // [H][LO]    gZ_last: row = hidden unit, k = outputs, natural
+  static constexpr int WOT = W0R + K0P * LH;  // [1][LH]    output layer: row = output 0 (outputs 1..15 are zeros), k = hidden units, permuted
+  static constexpr int WOR = WOT + LH;        // [H][LO]    gZ_last: row = hidden unit, k = outputs 0..3 (4..15 are zeros), natural
   static constexpr int WEND = (WOR + H * LO + 7) / 8 * 8;
   static constexpr int LIA = rows_img_ld(H), LIB = rows_img_ld(K0P);
   static constexpr int IMG_A = 32 * LIA, IMG_B = 32 * LIB;
@@ -55,6 +66,9 @@ struct Plan {
   static_assert((size_t)SCR * 2 >= (size_t)32 * NPL * C * 4, "the per-plane gradient factors fit the wave's image pair");
   static_assert((size_t)NGW * 4 <= (size_t)NW * SCR * 2, "the weight-gradient reduction reuses the waves' scratch");
   static_assert((TAPS * 2) % 16 == 0, "taps region 16-byte aligned");
+  static_assert((WOT * 2) % 16 == 0 && (WOR * 2) % 8 == 0, "the output layer's images are read 16 and 8 bytes at a time");
+  static_assert(NW != 4 || lds_alloc(BYTES) + 3 * lds_alloc(PASS_B_LDS) <= (size_t)LDS_PER_CU,
+                "one workgroup of this kernel and three of the field scatter's pass B fit one CU's LDS");
 };
 
 struct Level {
@@ -86,7 +100,8 @@ __device__ __forceinline__ V pick6(int q, V v0, V v1, V v2, V v3, V v4, V v5) {
   return r;
 }
 
-// two waves per SIMD (<= 256 registers, 0 B scratch: 242 VGPRs); with 4-wave workgroups and 66 KB of LDS that is two workgroups per CU
+// two waves per SIMD (<= 256 registers, 0 B scratch: 245 VGPRs); with 4-wave workgroups and 62 KB of LDS that is two workgroups per CU, or one
+// beside three workgroups of pass B (launch_density_bwd's budget)
 // CT: 1 = contracted coordinates (snerf_coords.contract of both levels; load_coords_ray).  Compile time: the run-time branch cost the bf16
 // kernel a spilled register.
 template <typename T, int NW, int CT = 0>
@@ -119,13 +134,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
     const float* WO = a.W + C * H;
 #pragma unroll
-    for (int i = 0; i < (16 * H + NT - 1) / NT; ++i) {  // WOT[o][p] = WO[pi(p)][o];  WOR[u][o] = WO[u][o]
+    for (int i = 0; i < (H * P::LO + NT - 1) / NT; ++i) {  // WOT[0][p] = WO[pi(p)][0];  WOR[u][o] = WO[u][o], o < 4
       const int idx = threadIdx.x + i * NT;
-      if (idx < 16 * H) {
-        const int o = idx / H, p = idx - o * H;
-        const int u2 = idx / 16, o2 = idx - u2 * 16;
-        const float v1 = WO[rows_pi(p)], v2 = WO[u2];
-        smem[P::WOT + o * P::LH + p] = Ops<T>::cvt(o < 1 ? v1 : 0.f);
+      if (idx < H) smem[P::WOT + idx] = Ops<T>::cvt(WO[rows_pi(idx)]);
+      if (idx < H * P::LO) {
+        const int u2 = idx / P::LO, o2 = idx - u2 * P::LO;
+        const float v2 = WO[u2];
         smem[P::WOR + u2 * P::LO + o2] = Ops<T>::cvt(o2 < 1 ? v2 : 0.f);
       }
     }
@@ -280,10 +294,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     v4t G0[2];
     {
       f32x4 y[2] = {};
-      const T* wrow = smem + P::WOT + c * P::LH + 8 * g;
+      const T* wrow = smem + P::WOT + 8 * g;
 #pragma unroll
       for (int s = 0; s < HK; ++s) {
-        const v8t w = ld8(wrow + 32 * s);
+        v8t w = ld8(wrow + 32 * s);
+        if (c >= 1) w = v8t{};  // rows 1..15 of the 16-wide image: zeros
 #pragma unroll
         for (int sl = 0; sl < 2; ++sl) y[sl] = Ops<T>::mfma(w, A1[sl][s], y[sl]);
       }
@@ -317,7 +332,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
       f32x4 d[2][HB];
 #pragma unroll
       for (int hb = 0; hb < HB; ++hb) {
-        const v4t w = *reinterpret_cast<const v4t*>(smem + P::WOR + (16 * hb + c) * P::LO + 4 * g);
+        v4t w = *reinterpret_cast<const v4t*>(smem + P::WOR + (16 * hb + c) * P::LO);
+        if (g >= 1) w = v4t{};  // columns 4..15 of the 16-wide image: zeros
 #pragma unroll
         for (int sl = 0; sl < 2; ++sl) {
           f32x4 acc = {};
@@ -489,8 +505,11 @@ static bool density_bwd_shape_ok(const snerf_kplanes_desc* d, const snerf_mlp_de
          (m->operands == 1 || m->operands == 2) && m->out_act == 0 && (m->hidden_act == 0 || m->hidden_act == 1);
 }
 
+// max_workgroups: the residency budget (snerf_kplanes_density_bwd_budget); <= 0 = every workgroup the device holds at once.  The workgroups are
+// persistent (each stays until its range of pairs is done), so two per CU leave a SIMD 16 registers and the CU 33 KB of LDS: nothing else starts
+// a wave there until the launch ends.  A smaller grid gives each workgroup a longer range and leaves CUs, or half of every CU, to the stream beside it.
 template <typename T, int CT>
-static int launch_density_bwd(pbwd::Args& a, const int64_t* pairs, int n_levels, hipStream_t st) {
+static int launch_density_bwd(pbwd::Args& a, const int64_t* pairs, int n_levels, int max_workgroups, hipStream_t st) {
   constexpr int NW = 4;  // 8-wave workgroups (mlp_rows' shape) would need 121 KB of LDS: one per CU
   using P = pbwd::Plan<NW>;
   auto k = pbwd::density_bwd_kernel<T, NW, CT>;
@@ -507,6 +526,7 @@ static int launch_density_bwd(pbwd::Args& a, const int64_t* pairs, int n_levels,
   const int64_t waves_needed = (total + 1) / 2;  // at least two pairs per wave
   int64_t grid = (waves_needed + NW - 1) / NW;
   if (grid > resident) grid = resident;
+  if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
   if (grid < n_levels) grid = n_levels;
   int g0 = n_levels > 1 ? (int)((grid * pairs[0] + total / 2) / total) : (int)grid;
   if (n_levels > 1) {
@@ -529,6 +549,10 @@ using namespace snerf;
 extern "C" int snerf_kplanes_density_bwd_supported(const snerf_kplanes_desc* desc, const snerf_mlp_desc* net) { return density_bwd_shape_ok(desc, net) ? 1 : 0; }
 
 extern "C" int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, int32_t n_levels, snerf_stream_t stream) {
+  return snerf_kplanes_density_bwd_budget(levels, n_levels, 0, stream);
+}
+
+extern "C" int snerf_kplanes_density_bwd_budget(const snerf_density_bwd_level* levels, int32_t n_levels, int32_t max_workgroups, snerf_stream_t stream) {
   SNERF_REQUIRE(levels && (n_levels == 1 || n_levels == 2), "kplanes_density_bwd: n_levels=%d (1 or 2)", n_levels);
   pbwd::Args a = {};
   int64_t pairs[2] = {0, 0};
@@ -562,6 +586,8 @@ extern "C" int snerf_kplanes_density_bwd(const snerf_density_bwd_level* levels, 
   }
   if (live == 0) return 0;
   if (contract == 1)
-    return operands == 2 ? launch_density_bwd<fp16, 1>(a, pairs, live, (hipStream_t)stream) : launch_density_bwd<bf16, 1>(a, pairs, live, (hipStream_t)stream);
-  return operands == 2 ? launch_density_bwd<fp16, 0>(a, pairs, live, (hipStream_t)stream) : launch_density_bwd<bf16, 0>(a, pairs, live, (hipStream_t)stream);
+    return operands == 2 ? launch_density_bwd<fp16, 1>(a, pairs, live, max_workgroups, (hipStream_t)stream)
+                         : launch_density_bwd<bf16, 1>(a, pairs, live, max_workgroups, (hipStream_t)stream);
+  return operands == 2 ? launch_density_bwd<fp16, 0>(a, pairs, live, max_workgroups, (hipStream_t)stream)
+                       : launch_density_bwd<bf16, 0>(a, pairs, live, max_workgroups, (hipStream_t)stream);
 }

@@ -134,6 +134,13 @@ class KPlanesTrainConfig:
     # crosses HBM.  gX bit-identical to the unfused net backward, plane / weight gradients the same terms in a longer run-length grouping.
     # Needs fused_proposal (16-bit operands) and the weight-gradient workspaces; never in deterministic mode.  False = the unfused kernels (A-B).
     fused_proposal_backward: bool = True
+    # Residency budget of that launch, in workgroups per CU (snerf_kplanes_density_bwd_budget; the trainer multiplies by the device's CU count and
+    # rounds).  0 = uncapped: the persistent grid takes two workgroups per CU, which hold 496 of a SIMD's 512 registers until the launch ends, so pass B
+    # of the field scatter, enqueued on the sweep's stream ~60 us behind it, starts no wave before that.  At 1.0 one workgroup per CU
+    # leaves room for three of pass B's beside it: the launch itself takes 0.77 ms instead of 0.41, pass B ends ~0.16 ms earlier and the headline
+    # drops ~3 % (1.25 about the same, 1.5 half of it: profiles/r28_prop_budget_INDEX.md).  The results are the same terms in a longer run-length
+    # grouping (gX bit for bit).
+    proposal_backward_workgroups_per_cu: float = 1.0
     # Round 4: inside train_step (single GPU) pass B of the field scatter is issued on the optimiser sweep's stream, in front of the sweep, instead of
     # on the caller's stream: the caller's stream is then free as soon as the sigma_net backward is queued, so the NEXT step's head (pixel draw, ray
     # generation, proposal levels) runs beside pass B (bound by float atomics) and has mostly finished when the sweep (bound by HBM) starts; and the
@@ -386,6 +393,12 @@ class KPlanesTrainer(FusedStep):
                                             and all(f"prop{i}.mlp" in self._mlp_ws for i in range(len(self.prop_nets)))
                                             and all(self.lib.snerf_kplanes_density_bwd_supported(C.byref(dp), C.byref(net.desc))
                                                     for dp, net in zip(self._desc_prop, self.prop_nets)))
+        if cfg.proposal_backward_workgroups_per_cu < 0:
+            raise ValueError(f"proposal_backward_workgroups_per_cu={cfg.proposal_backward_workgroups_per_cu} (0 = uncapped, or workgroups per CU)")
+        self._prop_bwd_workgroups = 0  # snerf_kplanes_density_bwd_budget: 0 = the whole resident grid
+        if cfg.proposal_backward_workgroups_per_cu > 0 and self.fused_proposal_backward:
+            cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
+            self._prop_bwd_workgroups = max(1, int(round(cfg.proposal_backward_workgroups_per_cu * cus)))
         if self.world > 1:
             self._plan_exchange()
 
@@ -797,16 +810,7 @@ class KPlanesTrainer(FusedStep):
             # both levels' net backward + plane scatter in one launch (snerf_kplanes_density_bwd), behind the two weights backwards
             for lvl in (0, 1):
                 wb(lvl)
-            levels = (_lib.DensityBwdLevel * 2)()
-            for lvl in (0, 1):
-                L, net = levels[lvl], self.prop_nets[lvl]
-                L.desc, L.planes, L.coords = C.addressof(self._desc_prop[lvl]), self.prop_planes[lvl].planes.data_ptr(), C.addressof(self._coords[lvl])
-                L.N, L.net, L.W, L.gdens = R * self.S[lvl], C.addressof(net.desc), net.params.data_ptr(), b["gdens"][lvl].data_ptr()
-                L.grad_planes, L.workspace = self.gviews[f"prop{lvl}.planes"].data_ptr(), self._mlp_ws[f"prop{lvl}.mlp"].data_ptr()
-                L.gX = b["gpfeat"][lvl].data_ptr() if cfg.ray_gradients else None
-                self._ws_dirty.add(f"prop{lvl}.mlp")
-            with self._span("kplanes_density_bwd"):
-                self._call("kplanes_density_bwd", levels, 2, self._st)
+            self._fused_proposal_backward()
         elif cfg.interleave_proposal_levels:
             for stage in (wb, nb, sc):
                 for lvl in (0, 1):
@@ -820,6 +824,21 @@ class KPlanesTrainer(FusedStep):
             # this stream; the nerf level adds behind them (backward())
             for lvl in (0, 1):
                 self._ray_gradient(self._desc_prop[lvl], self.prop_planes[lvl].planes, self._coords[lvl], R * self.S[lvl], b["gpfeat"][lvl])
+
+    def _fused_proposal_backward(self):
+        """Both levels' net backward + plane scatter from buf["gdens"] in one launch on the current stream, under the residency budget
+        (cfg.proposal_backward_workgroups_per_cu)."""
+        cfg, b, R = self.cfg, self.buf, self.R
+        levels = (_lib.DensityBwdLevel * 2)()
+        for lvl in (0, 1):
+            L, net = levels[lvl], self.prop_nets[lvl]
+            L.desc, L.planes, L.coords = C.addressof(self._desc_prop[lvl]), self.prop_planes[lvl].planes.data_ptr(), C.addressof(self._coords[lvl])
+            L.N, L.net, L.W, L.gdens = R * self.S[lvl], C.addressof(net.desc), net.params.data_ptr(), b["gdens"][lvl].data_ptr()
+            L.grad_planes, L.workspace = self.gviews[f"prop{lvl}.planes"].data_ptr(), self._mlp_ws[f"prop{lvl}.mlp"].data_ptr()
+            L.gX = b["gpfeat"][lvl].data_ptr() if cfg.ray_gradients else None
+            self._ws_dirty.add(f"prop{lvl}.mlp")
+        with self._span("kplanes_density_bwd"):
+            self._call("kplanes_density_bwd_budget", levels, 2, self._prop_bwd_workgroups, self._st)
 
     def _ray_gradient(self, desc, planes, coords, N, gfeat):
         """ray_grads += d(sum gfeat . features) / d(ray origins, directions) of one sampling level (snerf_kplanes_gather_bwd_coords)."""

@@ -90,6 +90,72 @@ def bench_field_fwd(dev, R=4096, repeats=5, iters=50):
         print(f"  {k:12s} us: " + " ".join(f"{x:7.1f}" for x in v) + f"   median {s[len(s) // 2]:.1f}  min {s[0]:.1f}  max {s[-1]:.1f}")
 
 
+def bench_prop_bwd_budget(dev, wg_per_cu, R=4096, repeats=5, iters=20, lag_us=100.0):
+    """The fused proposal backward (snerf_kplanes_density_bwd_budget) at a residency budget of `wg_per_cu` workgroups per CU (0 = uncapped), on the
+    state a training step of the preset leaves behind (bench.py's data): alone, and with pass B of the field scatter on a second stream, enqueued
+    `lag_us` behind it -- the situation of a step that updates the proposal networks.  Both streams are held back by a spin kernel while the host
+    enqueues, so the lag is the device's, not the host's.  Spans are between HIP events around each kernel (an event's time is the dispatch)."""
+    import ctypes as C
+    from soccernerfs_amd import synthetic
+    from soccernerfs_amd.fused_step import _On
+    from soccernerfs_amd.streams import side_stream
+    from soccernerfs_amd.trainer import KPlanesTrainConfig, KPlanesTrainer
+
+    torch.manual_seed(20231029)
+    tr = KPlanesTrainer(KPlanesTrainConfig(proposal_backward_workgroups_per_cu=wg_per_cu), R, dev)
+    tr.step = 20
+    cams = synthetic.make_cameras(20, 960, 540)
+    data = synthetic.render_dataset(cams, synthetic.frame_times(100, 3), list(range(19)), dev, chunk_rows=540)
+    M, H, W = data["images"].shape[:3]
+    for _ in range(4):  # the early schedule updates the proposal networks every second step: gdens, the sorted records and G are a step's own
+        idx, target = ops.sample_pixels_uniform(torch.rand(R, 3, device=dev), M, H, W, data["images"])
+        rays = ops.generate_rays(idx, data["fx"], data["fy"], data["cx"], data["cy"], data["c2w"], data["times"], aabb=tr.aabb, near_plane=tr.cfg.near_plane,
+                                 training=True)
+        tr.train_step(rays, target)
+    tr.synchronize()
+    assert tr.fused_proposal_backward and tr.quotient_scatter
+    main, side = torch.cuda.current_stream(), side_stream(dev, "bench_pass_b")
+    n_scales = tr._desc_field.n_scales
+    pass_b = lambda: tr._ss.quotient_pass_b_scales(tr.field_planes.planes, tr.gviews["field.planes"], 0, n_scales, C.c_void_p(side.cuda_stream))
+    t0 = time.perf_counter()
+    torch.cuda._sleep(10_000_000)
+    torch.cuda.synchronize()
+    cyc_per_us = 10_000_000 / ((time.perf_counter() - t0) * 1e6)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def once(with_fused, with_b):
+        a0, a1, b0, b1, go = ev(), ev(), ev(), ev(), ev()
+        torch.cuda._sleep(int(400 * cyc_per_us))  # the host enqueues everything below while this spins
+        go.record(main)
+        side.wait_event(go)
+        a0.record(main)
+        if with_fused:
+            with _On(tr, main):
+                tr._fused_proposal_backward()
+        a1.record(main)
+        with torch.cuda.stream(side):
+            if with_fused:
+                torch.cuda._sleep(int(lag_us * cyc_per_us))
+            b0.record(side)
+            if with_b:
+                pass_b()
+            b1.record(side)
+        torch.cuda.synchronize()
+        return a0.elapsed_time(a1) * 1e3, b0.elapsed_time(b1) * 1e3, max(a0.elapsed_time(a1), a0.elapsed_time(b1)) * 1e3, a0.elapsed_time(b0) * 1e3
+
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"proposal backward at {wg_per_cu:g} workgroups per CU ({tr._prop_bwd_workgroups or 'resident'} workgroups), R = {R}; medians of {iters} launches, {repeats} rounds")
+    for _ in range(repeats):
+        for _ in range(3):
+            once(True, True)
+        alone = med([once(True, False)[0] for _ in range(iters)])
+        b_alone = med([once(False, True)[1] for _ in range(iters)])
+        both = [once(True, True) for _ in range(iters)]
+        print(f"  fused backward alone {alone:7.1f} us | pass B alone {b_alone:7.1f} us | together: fused {med([x[0] for x in both]):7.1f} us, pass B {med([x[1] for x in both]):7.1f} us "
+              f"(enqueued {med([x[3] for x in both]):6.1f} us behind), first start to last end {med([x[2] for x in both]):7.1f} us")
+    tr.grads.zero_()
+
+
 def _int_flag(name, default):
     return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
@@ -100,6 +166,8 @@ def main():
         return bench_sort(dev)
     if "--field-fwd" in sys.argv[1:]:  # the fused field forward alone, nothing else
         return bench_field_fwd(dev, repeats=_int_flag("--repeats", 5), iters=_int_flag("--iters", 50))
+    if "--prop-bwd-wg-per-cu" in sys.argv[1:]:  # the fused proposal backward at a residency budget, alone and with pass B beside it
+        return bench_prop_bwd_budget(dev, float(sys.argv[sys.argv.index("--prop-bwd-wg-per-cu") + 1]), repeats=_int_flag("--repeats", 5), iters=_int_flag("--iters", 20))
     R = 4096
     res = {}
     # main field: 5 scales, C=32

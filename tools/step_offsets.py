@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--sort-before-field-fwd", action="store_true")
     ap.add_argument("--pipeline-sweep", default="off", choices=["coarse_first", "fine_first", "off"])
     ap.add_argument("--no-fused-proposal-backward", action="store_true", help="unfused net backward + plane scatter per proposal level (A-B)")
+    ap.add_argument("--prop-bwd-wg-per-cu", type=float, default=None, help="residency budget of the fused proposal backward in workgroups per CU "
+                    "(KPlanesTrainConfig.proposal_backward_workgroups_per_cu; 0 = uncapped; default: the config's)")
     ap.add_argument("--frames", type=int, default=2, help="frame times in the data set (bench.py's headline has 33; with the default 2 every batch holds two "
                     "times, so the time planes' rows are shared whatever the order of the rays and the field forward runs ~0.1 ms shorter than in the headline)")
     args = ap.parse_args()
@@ -31,6 +33,8 @@ def main():
     R = 4096
     cfg = KPlanesTrainConfig(interleave_proposal_levels=args.interleave_prop_levels, sort_before_field_fwd=args.sort_before_field_fwd, pipeline_sweep="" if args.pipeline_sweep == "off" else args.pipeline_sweep,
                              fused_proposal_backward=not args.no_fused_proposal_backward)
+    if args.prop_bwd_wg_per_cu is not None:
+        cfg.proposal_backward_workgroups_per_cu = args.prop_bwd_wg_per_cu
     tr = KPlanesTrainer(cfg, R, dev)
     tr.step = args.start_step
     cams = synthetic.make_cameras(20, 960, 540)

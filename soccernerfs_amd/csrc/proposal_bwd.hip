@@ -24,7 +24,11 @@
 //    lanes read its 32-byte texel together): 24 loads in flight per lane;
 //  * net: lane (g, c) holds features 4g .. 4g+3 of sample c / 16 + c (mlp_rows' B-operand layout), moved there by one lane swap (xor 32);
 //  * walk: 16 lanes per group, lane = 8 half + ch (x-corner, channel) as in the unfused kernel; group k owns the (plane, row) streams 3k .. 3k+2
-//    of the 12; a sample's per-plane gradient factors (G = prefix * suffix, [32][6][8] fp32) and its four axis taps come from LDS.
+//    of the 12; a sample's per-plane gradient factors (G = prefix * suffix, [32][6][8] fp32) and its four axis taps come from LDS.  The pair
+//    is walked in blocks of U = 8 samples: one sample at a time every link (sample x stream) waited for its own LDS reads, and with one wave
+//    per SIMD (the residency budget) nothing hid that; a block's 12 x 8 reads are issued together and the run logic works on registers.
+#include <type_traits>
+
 #include "kplanes_common.hpp"
 #include "mlp_rows_common.hpp"
 
@@ -100,12 +104,15 @@ __device__ __forceinline__ V pick6(int q, V v0, V v1, V v2, V v3, V v4, V v5) {
   return r;
 }
 
-// two waves per SIMD (<= 256 registers, 0 B scratch: 245 VGPRs); with 4-wave workgroups and 62 KB of LDS that is two workgroups per CU, or one
+// two waves per SIMD (<= 256 registers, 0 B scratch: 236 VGPRs for bf16, 211-223 for fp16); with 4-wave workgroups and 62 KB of LDS that is two workgroups per CU, or one
 // beside three workgroups of pass B (launch_density_bwd's budget)
 // CT: 1 = contracted coordinates (snerf_coords.contract of both levels; load_coords_ray).  Compile time: the run-time branch cost the bf16
 // kernel a spilled register.
-template <typename T, int NW, int CT = 0>
+// WIDE: 0 = a flush addresses its texel by a 32-bit byte offset from the level's gradient view (the launcher checks that the view ends below
+// 2^31 bytes), 1 = by the 64-bit form.  U: samples per block of the walk.
+template <typename T, int NW, int CT = 0, int WIDE = 0, int U = 8>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) void density_bwd_kernel(Args args) {
+  static_assert(32 % U == 0, "a pair is a whole number of blocks");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   using P = Plan<NW>;
@@ -170,18 +177,103 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
   const int64_t p_begin = a.pairs * wl / nwl, p_end = a.pairs * (wl + 1) / nwl;
 
   // ---- the walk: group k = lane >> 4 owns (plane, row) streams 3k .. 3k + 2; lane = 8 half + ch.  Pending run per stream ----
-  const int li = lane & 15, half = li >> 3, ch = li & 7;
-  int pend_key[3] = {-1, -1, -1};
+  // A texel's key is what a flush addresses it by: the byte offset of this lane's float from the level's gradient view, or (WIDE) the texel
+  // index in its plane.  Both name the texel one to one within a stream, so runs end where they did.
+  typedef typename std::conditional<WIDE != 0, int, uint32_t>::type key_t;
+  key_t pend_key[3] = {(key_t)-1, (key_t)-1, (key_t)-1};
   float pend_val[3] = {0.f, 0.f, 0.f};
-  auto stream_of = [&](int j, int& q, int& r, int& ax, int& ay, int& W, int64_t& off) {
-    const int st = 3 * g + j;
-    q = st >> 1;
-    r = st & 1;
-    ax = pair_a<NPL>(q);
-    ay = pair_b<NPL>(q);
+  // A group's three streams lie in TWO planes, qa = 3k >> 1 and qa + 1: streams 0 and 2 in the first and the second, stream 1 in the first
+  // (even k) or the second (odd k); a stream's row is (j + k) & 1.  What belongs to the x axis (index, this lane's corner weight, the factor)
+  // is read and multiplied once per plane.  Per plane e: where its numbers lie in a sample's tap row (words) and factor row, the key's row
+  // step and lane term; per stream: where its y index lies (the y weight two words on).  Set before each pair's walk from a lane number the
+  // compiler takes for new (set_streams' caller): held in registers across the net, they put the kernel over the registers it is allocated.
+  int tXi[2], tXw[2], gQ[2], tYi[3];
+  key_t kRow[2], kLane[2];
+  int64_t wOff[3] = {0, 0, 0};  // WIDE, per stream: this lane's float of texel 0 of the plane
+  bool odd = false;
+  auto set_streams = [&](int ln) {
+    const int gw = ln >> 4, lw = ln & 15;
+    odd = (gw & 1) != 0;
     const int r0 = a.d.res[0][0] > 0 ? a.d.res[0][0] : 1, r1 = a.d.res[0][1] > 0 ? a.d.res[0][1] : 1, r2 = a.d.res[0][2] > 0 ? a.d.res[0][2] : 1;
-    W = pick6(q, r0, r0, r0, r1, r1, r2);
-    off = pick6(q, a.d.off[0][0], a.d.off[0][1], a.d.off[0][2], a.d.off[0][3], a.d.off[0][4], a.d.off[0][5]) + li;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int q = ((3 * gw) >> 1) + e;
+      tXi[e] = 4 * pair_a<NPL>(q);
+      tXw[e] = tXi[e] + 2 + (lw >> 3);
+      gQ[e] = q * C + (lw & 7);
+      const int W = pick6(q, r0, r0, r0, r1, r1, r2);
+      const int64_t off = pick6(q, a.d.off[0][0], a.d.off[0][1], a.d.off[0][2], a.d.off[0][3], a.d.off[0][4], a.d.off[0][5]) + lw;
+      kRow[e] = WIDE ? (key_t)W : (key_t)W * (key_t)(C * 4);
+      kLane[e] = WIDE ? (key_t)0 : (key_t)off * (key_t)4;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int st = 3 * gw + j, q = st >> 1;
+      tYi[j] = 4 * pair_b<NPL>(q) + (st & 1);
+      if constexpr (WIDE != 0) wOff[j] = pick6(q, a.d.off[0][0], a.d.off[0][1], a.d.off[0][2], a.d.off[0][3], a.d.off[0][4], a.d.off[0][5]) + lw;
+    }
+  };
+  char* const gbase = reinterpret_cast<char*>(a.gplanes);
+  // a pending run's sum goes out under the lane's own predicate; zero sums (a clamped column, samples without gradient) are not sent
+  auto flush = [&](int j, bool go) {
+    if (go & (pend_val[j] != 0.f)) {  // ONE predicate, and not the selects' own: the compiler then keeps the selects and skips no block
+      if constexpr (WIDE != 0) atomicAdd(a.gplanes + wOff[j] + (int64_t)pend_key[j] * C, pend_val[j]);
+      else atomicAdd(reinterpret_cast<float*>(gbase + pend_key[j]), pend_val[j]);
+    }
+  };
+  // UU consecutive samples of the pair from s0: every LDS read of the block is issued before the first use, keys and values are formed
+  // lane-parallel, then the run logic goes over registers in sample order (per stream the additions and the flushes of the one-sample walk)
+  auto walk = [&](int s0, auto nu) {
+#pragma clang fp contract(off)
+    constexpr int UU = decltype(nu)::value;
+    int xi[UU][2], yi[UU][3];
+    float wx[UU][2], gf[UU][2], wy[UU][3];
+#pragma unroll
+    for (int u = 0; u < UU; ++u) {
+      const int* ts = taps + (s0 + u) * 16;
+      const float* gs = Gs + (s0 + u) * (NPL * C);
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        xi[u][e] = ts[tXi[e]];
+        wx[u][e] = __int_as_float(ts[tXw[e]]);
+        gf[u][e] = gs[gQ[e]];
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        yi[u][j] = ts[tYi[j]];
+        wy[u][j] = __int_as_float(ts[tYi[j] + 2]);
+      }
+    }
+    key_t key[UU][3];
+    float val[UU][3];
+    const key_t kRow1 = odd ? kRow[1] : kRow[0];
+#pragma unroll
+    for (int u = 0; u < UU; ++u) {
+      key_t kx[2];
+      float gq[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        kx[e] = WIDE ? (key_t)xi[u][e] : (key_t)xi[u][e] * (key_t)(C * 4) + kLane[e];
+        gq[e] = gf[u][e] * wx[u][e];
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const key_t kxj = j == 0 ? kx[0] : (j == 2 ? kx[1] : (odd ? kx[1] : kx[0]));
+        const key_t krj = j == 0 ? kRow[0] : (j == 2 ? kRow[1] : kRow1);
+        const float gqj = j == 0 ? gq[0] : (j == 2 ? gq[1] : (odd ? gq[1] : gq[0]));
+        key[u][j] = (key_t)yi[u][j] * krj + kxj;
+        val[u][j] = gqj * wy[u][j];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UU; ++u)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const bool cut = key[u][j] != pend_key[j];
+        flush(j, cut);
+        pend_val[j] = cut ? val[u][j] : pend_val[j] + val[u][j];
+        pend_key[j] = key[u][j];
+      }
   };
 
   const int sl_g = g >> 1, hc = g & 1;  // gather: sample 16 sl_g + c of the pair, channels 4 hc .. 4 hc + 3
@@ -416,40 +508,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     // ---- walk: run-length combined scatter along the wave's range ----
     {
       const int cnt = (int)((a.N - pair * 32) < 32 ? (a.N - pair * 32) : 32);
-      int wq[3], wr[3], wa[3], wb[3], wW[3];
-      int64_t woff[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) stream_of(j, wq[j], wr[j], wa[j], wb[j], wW[j], woff[j]);
-      for (int s = 0; s < cnt; ++s) {
-        const int4* ts = reinterpret_cast<const int4*>(taps + s * 16);
-        const float* gs = Gs + s * (NPL * C) + ch;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const int4 tx = ts[wa[j]], ty = ts[wb[j]];
-          const float wx = __int_as_float(half ? tx.w : tx.z);
-          const float wy = __int_as_float(wr[j] ? ty.w : ty.z);
-          const float gq = gs[wq[j] * C] * wx;
-          const float val = gq * wy;
-          const int key = (wr[j] ? ty.y : ty.x) * wW[j] + tx.x;
-          if (key != pend_key[j]) {
-            if (pend_val[j] != 0.f) atomicAdd(a.gplanes + woff[j] + (int64_t)pend_key[j] * C, pend_val[j]);
-            pend_key[j] = key;
-            pend_val[j] = val;
-          } else {
-            pend_val[j] += val;
-          }
-        }
-      }
+      int ln = lane;
+      asm volatile("" : "+v"(ln));  // opaque: the streams' constants are formed here, per pair, from a few selects
+      set_streams(ln);
+      int s = 0;  // whole blocks, then a short last pair's remainder one sample at a time (rows past cnt are never read)
+      for (; s + U <= cnt; s += U) walk(s, std::integral_constant<int, U>{});
+      for (; s < cnt; ++s) walk(s, std::integral_constant<int, 1>{});
     }
     wave_lds_publish();  // the walk's reads are done before the next pair's taps and images
   }
+  set_streams(lane);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    int q, r, ax, ay, W;
-    int64_t off;
-    stream_of(j, q, r, ax, ay, W, off);
-    if (pend_val[j] != 0.f) atomicAdd(a.gplanes + off + (int64_t)pend_key[j] * C, pend_val[j]);
-  }
+  for (int j = 0; j < 3; ++j) flush(j, true);
 
   // ---- weight gradients: sum the workgroup's waves through LDS (mlp_rows' fixed order), then one atomic per element into the workspace ----
   {
@@ -508,11 +578,11 @@ static bool density_bwd_shape_ok(const snerf_kplanes_desc* d, const snerf_mlp_de
 // max_workgroups: the residency budget (snerf_kplanes_density_bwd_budget); <= 0 = every workgroup the device holds at once.  The workgroups are
 // persistent (each stays until its range of pairs is done), so two per CU leave a SIMD 16 registers and the CU 33 KB of LDS: nothing else starts
 // a wave there until the launch ends.  A smaller grid gives each workgroup a longer range and leaves CUs, or half of every CU, to the stream beside it.
-template <typename T, int CT>
+template <typename T, int CT, int WIDE>
 static int launch_density_bwd(pbwd::Args& a, const int64_t* pairs, int n_levels, int max_workgroups, hipStream_t st) {
   constexpr int NW = 4;  // 8-wave workgroups (mlp_rows' shape) would need 121 KB of LDS: one per CU
   using P = pbwd::Plan<NW>;
-  auto k = pbwd::density_bwd_kernel<T, NW, CT>;
+  auto k = pbwd::density_bwd_kernel<T, NW, CT, WIDE>;
   SNERF_ALLOW_LDS(k, P::BYTES);
   // persistent grid sized to residency: as many workgroups as fit on the device at once, split between the levels by their pair counts
   static int resident = 0;
@@ -557,6 +627,7 @@ extern "C" int snerf_kplanes_density_bwd_budget(const snerf_density_bwd_level* l
   pbwd::Args a = {};
   int64_t pairs[2] = {0, 0};
   int operands = 0, live = 0, contract = -1;
+  bool wide = false;  // a level's gradient view reaches 2^31 bytes: the kernel's 32-bit texel offsets do not span it
   for (int l = 0; l < n_levels; ++l) {
     const snerf_density_bwd_level& L = levels[l];
     SNERF_REQUIRE(L.desc && L.coords && L.net, "kplanes_density_bwd: null descriptor (level %d)", l);
@@ -578,6 +649,12 @@ extern "C" int snerf_kplanes_density_bwd_budget(const snerf_density_bwd_level* l
                                       : (L.coords->origins && L.coords->dirs && L.coords->ebins && L.coords->times && L.coords->S > 0),
                   "kplanes_density_bwd: incomplete coordinates (level %d)", l);
     SNERF_REQUIRE(!L.gX || (reinterpret_cast<uintptr_t>(L.gX) & 15) == 0, "kplanes_density_bwd: gX must be 16-byte aligned");
+    for (int q = 0; q < pbwd::NPL; ++q) {
+      SNERF_REQUIRE(L.desc->off[0][q] >= 0, "kplanes_density_bwd: off[0][%d]=%lld (level %d)", q, (long long)L.desc->off[0][q], l);
+      const int64_t texels = (int64_t)L.desc->res[0][pair_a<pbwd::NPL>(q)] * L.desc->res[0][pair_b<pbwd::NPL>(q)];
+      // one texel past the plane: the x0 + 1 corner of a clamped column forms (and never sends) that address
+      if ((L.desc->off[0][q] + (texels + 1) * pbwd::C) * 4 >= (1LL << 31)) wide = true;
+    }
     pbwd::Level& o = a.lv[live];
     o.d = *L.desc; o.c = *L.coords; o.planes = L.planes; o.W = L.W; o.gdens = L.gdens; o.gplanes = L.grad_planes; o.ws = L.workspace; o.gX = L.gX;
     o.N = L.N; o.pairs = (L.N + 31) / 32; o.ws_stride = (snerf_mlp_param_count(L.net) + 63) / 64 * 64; o.relu = L.net->hidden_act == 1;
@@ -585,9 +662,13 @@ extern "C" int snerf_kplanes_density_bwd_budget(const snerf_density_bwd_level* l
     ++live;
   }
   if (live == 0) return 0;
-  if (contract == 1)
-    return operands == 2 ? launch_density_bwd<fp16, 1>(a, pairs, live, max_workgroups, (hipStream_t)stream)
-                         : launch_density_bwd<bf16, 1>(a, pairs, live, max_workgroups, (hipStream_t)stream);
-  return operands == 2 ? launch_density_bwd<fp16, 0>(a, pairs, live, max_workgroups, (hipStream_t)stream)
-                       : launch_density_bwd<bf16, 0>(a, pairs, live, max_workgroups, (hipStream_t)stream);
+  auto launch = [&](auto ct, auto wd) {
+    constexpr int CT = decltype(ct)::value, WD = decltype(wd)::value;
+    return operands == 2 ? launch_density_bwd<fp16, CT, WD>(a, pairs, live, max_workgroups, (hipStream_t)stream)
+                         : launch_density_bwd<bf16, CT, WD>(a, pairs, live, max_workgroups, (hipStream_t)stream);
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  if (contract == 1) return wide ? launch(I1{}, I1{}) : launch(I1{}, I0{});
+  return wide ? launch(I0{}, I1{}) : launch(I0{}, I0{});
 }

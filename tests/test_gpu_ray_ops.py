@@ -1,8 +1,12 @@
 """GPU parity: per-ray sampling ops (HIP, through the C ABI) vs golden vectors and the CPU oracle.
-Sample indices must be bit-exact; bins <= 1e-6 abs; weights rtol 1e-5; gradients rtol 1e-4."""
+Sample indices must be bit-exact; bins <= 1e-6 abs; weights rtol 1e-5; gradients rtol 1e-4.  Where the weights are given and
+anneal == 1, indices and bins EQUAL the float32 restatement of tests/sampler_reference.py on every element, u formed in the kernel included
+(tests/test_gpu_sampler_lattice.py does the same over a lattice of shapes and edges)."""
+import numpy as np
 import pytest
 import torch
 
+from tests import sampler_reference as SR
 from tests.conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -46,17 +50,26 @@ def test_pdf_resample_golden_indices_bit_exact(tag):
     sb, eb, inds = ops.pdf_resample(prev.to(DEV), nears, fars, S, weights=w.to(DEV), u=u.to(DEV), return_inds=True)
     assert torch.equal(inds.cpu(), o_inds)
     assert torch.equal(inds.cpu(), g[f"{tag}_inds"])  # and to the reference's on this fixture
-    close(sb, o_bins, rtol=0, atol=1e-7)  # same arithmetic as the oracle (double-accumulated CDF)
+    assert SR.prefix_sums_off_midpoints({"weights": w.numpy(), "anneal": 1.0, "histogram_padding": 0.01, "eps": 1e-5})  # any order of summation
+    assert torch.equal(sb.cpu(), o_bins)  # same arithmetic as the oracle (double-accumulated CDF): every bin, bit for bit
     # vs the reference's own output: its CDF used torch.sum's association order; the inverse CDF amplifies that ulp
     close(sb, g[f"{tag}_new_sbins"], rtol=0, atol=5e-6)
     close(eb, g[f"{tag}_new_ebins"], rtol=1e-6, atol=2e-5)
     # (2) u built in-kernel from the random draws
     sb2, eb2, inds2 = ops.pdf_resample(prev.to(DEV), nears, fars, S, weights=w.to(DEV), rand=rand.to(DEV), return_inds=True)
+    # ... equals the restatement, whose u is the kernel's documented formula, on every element
+    u_k = SR.pdf_u(R, S, rand.numpy())
+    want = SR.pdf_sample(w.numpy(), prev.numpy(), u_k)
+    assert np.array_equal(inds2.cpu().numpy(), want["inds"]) and np.array_equal(sb2.cpu().numpy(), want["sbins"])
+    # ... and differs from the oracle's indices only where the restatement's u and torch.linspace's u differ (the last ulp of u)
     bad = inds2.cpu() != o_inds
-    assert int(bad.sum()) <= 2, int(bad.sum())  # only fp ties of u itself may differ
-    close(sb2[~bad.to(DEV)], o_bins[~bad], rtol=0, atol=5e-6)  # in-kernel u differs from torch.linspace in the last ulp
-    # (3) eval mode (u at bin centres): equal up to exact CDF ties (oracle docstring)
+    assert int(bad.sum()) <= 2, int(bad.sum())
+    assert bool((torch.from_numpy(u_k) != u)[bad].all())
+    close(sb2[~bad.to(DEV)], o_bins[~bad], rtol=0, atol=5e-6)
+    # (3) eval mode (u at bin centres): the restatement on every element; the oracle up to exact CDF ties (oracle docstring)
     sb3, eb3, inds3 = ops.pdf_resample(prev.to(DEV), nears, fars, S, weights=w.to(DEV), return_inds=True)
+    want = SR.pdf_sample(w.numpy(), prev.numpy(), SR.pdf_u(R, S, None))
+    assert np.array_equal(inds3.cpu().numpy(), want["inds"]) and np.array_equal(sb3.cpu().numpy(), want["sbins"])
     ue = KO.pdf_u(R, S, None)
     e_bins, e_inds, e_cdf = KO.pdf_sample(w, prev, ue)
     bad = inds3.cpu() != e_inds
@@ -86,8 +99,14 @@ def test_pdf_resample_indices_bit_exact_at_preset_sizes(tag):
     assert flips == 0
     close(sb, g[f"{tag}_new_sbins"], rtol=0, atol=5e-6)
     # u formed in-kernel from the draws (the training path): only fp ties of u itself may move an index
-    _, _, inds2 = ops.pdf_resample(prev.to(DEV), nears, fars, S, weights=w.to(DEV), rand=rand.to(DEV), return_inds=True)
-    assert int((inds2.cpu() != ref).sum()) <= 4, int((inds2.cpu() != ref).sum())
+    sb2, _, inds2 = ops.pdf_resample(prev.to(DEV), nears, fars, S, weights=w.to(DEV), rand=rand.to(DEV), return_inds=True)
+    assert SR.prefix_sums_off_midpoints({"weights": w.numpy(), "anneal": 1.0, "histogram_padding": 0.01, "eps": 1e-5})
+    u_k = SR.pdf_u(R, S, rand.numpy())
+    want = SR.pdf_sample(w.numpy(), prev.numpy(), u_k)  # the restatement, whose u is the kernel's documented formula: every element
+    assert np.array_equal(inds2.cpu().numpy(), want["inds"]) and np.array_equal(sb2.cpu().numpy(), want["sbins"])
+    bad = inds2.cpu() != ref  # the reference's recorded indices: differs only where the restatement's u and torch.linspace's u differ
+    assert int(bad.sum()) <= 4, int(bad.sum())
+    assert bool((torch.from_numpy(u_k) != u)[bad].all())
 
 
 def test_pdf_resample_anneal_and_fused_weights():
@@ -111,7 +130,13 @@ def test_pdf_resample_anneal_and_fused_weights():
                                           u=u.to(DEV), anneal=anneal, return_inds=True, return_weights=True)
     close(wout, w, rtol=1e-5, atol=1e-7)
     frac = float((inds.cpu() == o_inds).float().mean())
-    assert frac > 0.999, frac  # expf/powf differ from the CPU libm in the last ulp => rare tie flips
+    assert frac > 0.999, frac  # expf/powf differ from the CPU libm in the last ulp => rare tie flips ...
+    # ... and EVERY index lies where the float64 cdf puts u, within tau = 5 x the float32 restatement's own cdf deviation
+    case = {"R": R, "Sp": Sp, "S": S, "density": dens.numpy(), "ebins_prev": eb_prev.numpy(), "sbins_prev": sb_prev.numpy(), "nears": nears.numpy()[:, 0],
+            "fars": fars.numpy()[:, 0], "histogram_padding": 0.01, "eps": 1e-5, "anneal": anneal, "u": u.numpy(), "u_mode": 0}
+    ref64 = SR.reference(case, "uniform", SR.f64)
+    assert SR.index_within(inds.cpu().numpy(), ref64["cdf"], u.numpy().astype(np.float64), SR.TAU).all()
+    assert SR.bins_inside(inds.cpu().numpy(), sb.cpu().numpy(), sb_prev.numpy()).all()
     # The inverse CDF is ill-conditioned in low-density bins, so compare in the well-conditioned direction:
     # the oracle's piecewise-linear CDF evaluated at the kernel's bins must reproduce u.
     _, _, cdf = KO.pdf_sample(torch.pow(w, anneal), sb_prev, u)

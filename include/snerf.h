@@ -895,6 +895,19 @@ int snerf_tgrid_encode_bwd_fx(const snerf_tgrid_desc* desc, const snerf_coords* 
                               const float* times, int32_t samples_per_row, int64_t B, const float* grad_out, int64_t* grad_embeddings_fx,
                               snerf_stream_t stream);
 
+/* Added to ABI 16 revision 2's surface (see SNERF_ABI_REVISION): fused proposal density of a temporal-grid field =
+ * TemporalHashMLPDensityField.density_fn (NS/fields/nerfplayer_nerfacto_field.py:83-104: the TemporalGridEncoder, the L*C -> 16 -> 1 tcnn.Network
+ * and trunc_exp) as ProposalNetworkSampler calls it per level (NS/model_components/ray_samplers.py:559-600), in one kernel (csrc/tgrid_density.hip).
+ * Samples are the bin midpoints of rays (coords mode 1, coords->S == S, N = rays * S < 2^31), times [N / S] one per ray, W the net's weights in
+ * snerf_mlp_fwd's layout, density [N] = exp(net(encode(x, t))).  Bit-identical to snerf_tgrid_encode_fwd (times, samples_per_row = S) +
+ * snerf_mlp_fwd (aux_col 0 = trunc_exp); the [N, L*C] features and the raw output are not written anywhere.
+ *     _supported: 1 for D = 3, level_dim C = 2, L * C <= 16 (hash or tiled, any temporal_dim) with the net L*C -> 16 -> 1, one hidden layer, ReLU, no
+ *     output activation, fp32 operands (operands = 0); 0 for everything else -- those callers keep the two launches.  The entry refuses unsupported
+ *     shapes, mode-0 coordinates, contract != 0 and null buffers before it launches anything. */
+int snerf_tgrid_density_fwd_supported(const snerf_tgrid_desc* desc, const snerf_mlp_desc* net);
+int snerf_tgrid_density_fwd(const snerf_tgrid_desc* desc, const float* embeddings, const snerf_coords* coords, const float* times, int32_t S, int64_t N,
+                            const snerf_mlp_desc* net, const float* W, float* density, snerf_stream_t stream);
+
 /* ABI 14: the backward w.r.t. the table in OWNER-COMPUTES form, for D = 3 grids with per-sample / per-ray `times` (csrc/tgrid_tiles.hip).  Replaces the
  * same reference kernel (kernel_grid_backward, temporal_gridencoder.cu:283-370) and, in its fused form, the torch.optim.Adam step of the table that
  * follows it (NS/configs/method_configs.py:648-657) together with the temporal-TV gradient (NS/field_components/temporal_grid.py:352-376).  The table is

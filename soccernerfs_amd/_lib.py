@@ -260,6 +260,8 @@ SIGNATURES = {
     "snerf_tgrid_input_bwd": "s:PPLIIIPP",
     "snerf_tgrid_encode_bwd": "s:PPPPILPPP",
     "snerf_tgrid_encode_bwd_fx": "s:PPPPILPPP",
+    "snerf_tgrid_density_fwd_supported": "i:PP",
+    "snerf_tgrid_density_fwd": "s:PPPPILPPPP",
     "snerf_tgrid_tile_plan_make": "s:PLIIP",
     "snerf_tgrid_bwd_bin": "s:PPPPILPPPPPP",
     "snerf_tgrid_bwd_tiles": "s:PPLPPPPPP",

@@ -213,10 +213,7 @@ __global__ __launch_bounds__(256) void tgrid_runs_kernel(TgridArgs a, int segs, 
   float reg[8];  // per corner of the current (cell, column) -- BWD: the sum not yet sent; forward: the table value
 #pragma unroll
   for (int i = 0; i < 8; ++i) reg[i] = 0.f;
-  auto entry = [&](const uint32_t cell[3], int idx, int column) {
-    const uint32_t row = lv.row_of(cell[0] + (uint32_t)(idx & 1), cell[1] + (uint32_t)((idx >> 1) & 1), cell[2] + (uint32_t)(idx >> 2));
-    return ((size_t)lv.off0 + row) * (size_t)a.d.grid_C + (size_t)column;
-  };
+  auto entry = [&](const uint32_t cell[3], int idx, int column) { return tg_corner_entry(lv, a.d.grid_C, cell, idx, column); };
   auto flush = [&]() {
 #pragma unroll
     for (int idx = 0; idx < 8; ++idx) {
@@ -261,11 +258,7 @@ __global__ __launch_bounds__(256) void tgrid_runs_kernel(TgridArgs a, int segs, 
           ppg[0] = pg[0]; ppg[1] = pg[1]; ppg[2] = pg[2];
           pcol = col;
         }
-#pragma unroll
-        for (int idx = 0; idx < 8; ++idx) {
-          const float v = reg[idx] * wt;  // the temporal weight is applied per sample (explicit points: every sample has its own time), as tgrid_kernel does
-          acc += table_corner_weight(fr, 3, idx) * v;
-        }
+        acc = tg_cell_interp(reg, fr, wt);
       }
       acc += __shfl_xor(acc, 1, 64);  // column a + column b of this channel: a pair shares its group, hence its segment and trip count (see the launcher)
       if (ab == 0) a.out[b * stride + at] = oob ? 0.f : acc;

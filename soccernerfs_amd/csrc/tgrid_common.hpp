@@ -95,4 +95,23 @@ __device__ __forceinline__ void tg_cell(const TgLevel& lv, bool align_corners, c
   }
 }
 
+// ---- one sample's forward at one level, for the kernels that keep a cell's eight corner values in registers (D = 3: tgrid.hip's run-length
+// forward, tgrid_density.hip) ----
+// table element of corner idx (bit d: the far side of axis d) of `cell`, at `column` of its row
+__device__ __forceinline__ size_t tg_corner_entry(const TgLevel& lv, int grid_C, const uint32_t cell[3], int idx, int column) {
+  const uint32_t row = lv.row_of(cell[0] + (uint32_t)(idx & 1), cell[1] + (uint32_t)((idx >> 1) & 1), cell[2] + (uint32_t)(idx >> 2));
+  return ((size_t)lv.off0 + row) * (size_t)grid_C + (size_t)column;
+}
+// One (channel, column) slot's share of a sample's feature: the eight corner values times the slot's temporal weight, interpolated at in-cell position
+// fr -- tgrid_kernel<false>'s products and its order of the eight additions.  The feature is this plus the same of the channel's other column.
+__device__ __forceinline__ float tg_cell_interp(const float val[8], const float fr[3], float wt) {
+  float acc = 0.f;
+#pragma unroll
+  for (int idx = 0; idx < 8; ++idx) {
+    const float v = val[idx] * wt;  // the temporal weight is applied per sample (explicit points: every sample has its own time), as tgrid_kernel does
+    acc += table_corner_weight(fr, 3, idx) * v;
+  }
+  return acc;
+}
+
 }  // namespace snerf

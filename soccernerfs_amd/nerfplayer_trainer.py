@@ -230,3 +230,64 @@ class NerfplayerTrainer(NerfplayerStep):
         level's weights, compositing, MSE backward, distortion term and weights' backward are one launch and the expected DEPTH of the batch is not rendered
         (no loss of this model reads it: buf["depth"] keeps the last forward(training=False)'s values); forward() + backward() called separately render it."""
         return self._train_step(target, rng, rays, cams)
+
+    # ---- nerfstudio checkpoint files (trainer.py:331-380 of the reference; formats in soccernerfs_amd/checkpoint.py) ----
+    _CK_NAMES = {"field.mlp_base.embeddings": "field.table", "field.mlp_base_decode.params": "field.decode", "field.mlp_head.params": "field.head",
+                 "field.embedding_appearance.weight": "field.appearance",
+                 "proposal_networks.0.encoding.embeddings": "prop0.table", "proposal_networks.0.linear.params": "prop0.mlp",
+                 "proposal_networks.1.encoding.embeddings": "prop1.table", "proposal_networks.1.linear.params": "prop1.mlp"}
+
+    def _named_module(self) -> torch.nn.Module:
+        """The trainer's parameters under NerfplayerNerfactoModel's module names, registered in its order (nerfplayer_nerfacto.py,
+        nerfplayer_nerfacto_field.py), so a checkpoint's keys -- the temporal grids' index buffers and `embedding.weight` included -- are that model's."""
+        nn = torch.nn
+        root = nn.Module()
+        root.device_indicator_param = nn.Parameter(torch.empty(0))
+        aabb = lambda: nn.Parameter(torch.tensor(self.aabb, dtype=torch.float32), requires_grad=False)
+        root.field = nn.Module()
+        root.field.aabb = aabb()
+        root.field.embedding_appearance, root.field.mlp_base = self.appearance, self.enc
+        root.field.mlp_base_decode, root.field.mlp_head = self.decode, self.head
+        root.proposal_networks = nn.ModuleList()
+        for enc, net in zip(self.prop_enc, self.prop_mlp):
+            m = nn.Module()
+            m.aabb = aabb()
+            m.encoding, m.linear = enc, net
+            root.proposal_networks.append(m)
+        return root
+
+    def save_checkpoint(self, checkpoint_dir: str, save_only_latest_checkpoint: bool = True) -> str:
+        """Writes `step-%09d.ckpt` with the keys of NerfplayerNerfactoModel and the Adam moments of both parameter groups.  The saved step is the
+        index of the last completed iteration, as the reference saves it; load_checkpoint resumes at step + 1."""
+        from . import checkpoint as CK
+
+        self.synchronize()  # the asynchronous sweep and the tiled pass may still be writing the field table and its moments
+        moments = {ck: (self.mviews[seg], self.vviews[seg], self.step) for ck, seg in self._CK_NAMES.items()} if self.step > 0 else {}
+        root = self._named_module()
+        hyper = {"lr": self.lr, "betas": (0.9, 0.999), "eps": self.adam_eps, "weight_decay": 0, "amsgrad": False}
+        opt = CK.export_optimizer_states(root, moments, {"fields": hyper, "proposal_networks": hyper})
+        return CK.save_checkpoint(checkpoint_dir, max(self.step - 1, 0), root, opt, save_only_latest_checkpoint)
+
+    def load_checkpoint(self, load_dir: str, load_step: Optional[int] = None, params_only: bool = False) -> int:
+        """Parameters (+ Adam moments when the file holds them) from a nerfstudio checkpoint of this model; returns the step training resumes at.
+        params_only: the parameters are loaded, the moments are cleared and the optimiser restarts at step 0; returns 0."""
+        from . import checkpoint as CK
+
+        self.synchronize()
+        start, moments = CK.load_checkpoint(load_dir, self._named_module(), load_step)
+        self.grads.zero_()
+        if self.grads_fx is not None:
+            self.grads_fx.zero_()
+        self._steps_since_update, self._swept, self._sweeps_done = 0, (), None
+        if params_only or not moments:  # Adam's bias correction counts optimiser updates: without moments the optimiser restarts
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            self.step = 0
+        else:
+            for ck, (m, v, _) in moments.items():
+                seg = self._CK_NAMES[ck]
+                self.mviews[seg].copy_(m.reshape(self.mviews[seg].shape).to(self.dev))
+                self.vviews[seg].copy_(v.reshape(self.vviews[seg].shape).to(self.dev))
+            self.step = start
+        torch.cuda.synchronize(self.dev)
+        return 0 if params_only else start

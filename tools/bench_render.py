@@ -56,13 +56,148 @@ class LaunchCounter:
         fused_step.FusedStep._ck = self._ck
 
 
+def main_nerfplayer(args):
+    """--method nerfplayer-nerfacto: 960 x 540 frames of the config-4 shape (the nerfplayer-nerfacto preset, R = 4096, stadium-scene cameras) through
+      i    tools/train_psnr_nerfplayer.py::eval_psnr: index table, ops.generate_rays, NerfplayerTrainer.forward(training=False) in 4096-ray slices
+           (whole slices only; one host read-back per frame for its PSNR)
+      ii   NerfplayerRenderer, 32768-ray chunks, proposal density = snerf_tgrid_encode_fwd + snerf_mlp_fwd
+      iii  NerfplayerRenderer, proposal density = snerf_tgrid_density_fwd
+    alternating inside each round, and snerf_tgrid_density_fwd alone against the pair at N = 32768 x 256 and 32768 x 96 by HIP events."""
+    import ctypes as C
+
+    from soccernerfs_amd.nerfplayer_nerfacto import NerfplayerNerfactoModelConfig
+    from soccernerfs_amd.nerfplayer_trainer import NerfplayerTrainer
+    from soccernerfs_amd.render import NerfplayerRenderer
+    from tools.train_psnr_nerfplayer import eval_psnr
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    R, Wd, Hd = 4096, 960, 540
+    cams = synthetic.make_stadium_cameras(30, 6, Wd, Hd)
+    frame_ids = torch.linspace(0, 99, 8).long()
+    data = synthetic.render_dataset(cams, frame_ids.float() / 99, list(range(30)), dev, chunk_rows=Hd, variant="stadium")
+    held = synthetic.render_dataset(cams, frame_ids.float()[:1] / 99 + 0.37, list(range(30, 36)), dev, chunk_rows=Hd, variant="stadium")
+    M, H, W = data["images"].shape[:3]
+    tr = NerfplayerTrainer(NerfplayerNerfactoModelConfig(), R, M, aabb_scale=1.0, device=dev, mlp_operands=args.mlp_operands, async_field_sweep=True,
+                           tiled_field_backward=True)
+    state = "initialised (NerfplayerTrainer's own initialisation, no training)"
+    if args.load_dir:
+        tr.load_checkpoint(args.load_dir)
+        state = f"loaded from a checkpoint, resumes at step {tr.step}"
+    elif args.train_steps:
+        for _ in range(args.train_steps):
+            idx, target = ops.sample_pixels_uniform(torch.rand(R, 3, device=dev), M, H, W, data["images"])
+            rays = ops.generate_rays(idx, data["fx"], data["fy"], data["cx"], data["cy"], data["c2w"], data["times"])
+            tr.train_step(rays, idx[:, 0].contiguous(), target)
+        state = f"trained {args.train_steps} steps here on the synthetic stadium scene (no checkpoint at hand)"
+    tr.synchronize()
+    n_frames = min(args.frames, held["images"].shape[0])
+    frames = list(range(n_frames))
+    hcams = Cameras(held["c2w"], held["fx"], held["fy"], held["cx"], held["cy"], W, H, held["times"])
+    rn = {"ii": NerfplayerRenderer(tr, 32768, fused_density=False), "iii": NerfplayerRenderer(tr, 32768, fused_density=True)}
+    assert rn["iii"].fused_density == [True, True] and rn["ii"].fused_density == [False, False]
+    anneal = rn["ii"].default_anneal()
+    few = {k: v[:n_frames] if isinstance(v, torch.Tensor) and v.shape[0] == held["images"].shape[0] else v for k, v in held.items()}
+    arms = {"i": lambda: eval_psnr(tr, few, n_frames, anneal), "ii": lambda: [rn["ii"].render_frame(hcams, m, anneal=anneal)["rgb"] for m in frames],
+            "iii": lambda: [rn["iii"].render_frame(hcams, m, anneal=anneal)["rgb"] for m in frames]}
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t1) * 1e3 / n_frames)
+    launches = {}
+    with LaunchCounter() as lc:
+        eval_psnr(tr, {k: v[:1] if isinstance(v, torch.Tensor) and v.shape[0] == held["images"].shape[0] else v for k, v in held.items()}, 1, anneal)
+        launches["i"] = lc.n
+    for k, r in rn.items():
+        n0 = r.launches
+        r.render_frame(hcams, 0, anneal=anneal)
+        launches[k] = r.launches - n0
+    same_bits = all(torch.equal(a, b) for a, b in zip(arms["ii"](), arms["iii"]()))
+    groups = {}
+    for k, r in rn.items():
+        r.enable_kernel_timing()
+        for m in frames:
+            r.render_frame(hcams, m, anneal=anneal)
+        kt = r.kernel_times_ms()
+        r.disable_kernel_timing()
+        groups[k] = {name: round(v[0] * v[1] / n_frames, 3) for name, v in sorted(kt.items())}
+
+    # the kernel alone against the pair: a full 32768-ray chunk of the last frame's rays and bins, level by level
+    r3, kernel = rn["iii"], {}
+    o, d, t = (r3._rays[q] for q in ("origins", "directions", "times"))
+    for lvl, S in enumerate(tr.S[:2]):
+        enc, net, N = tr.prop_enc[lvl], tr.prop_mlp[lvl], 32768 * tr.S[lvl]
+        co = ops.coords_from_rays(o, d, t, r3.buf["eb"][lvl], tr.aabb, False)
+        dens_f, dens_p = torch.empty(N, device=dev), torch.empty(N, device=dev)
+        feat, raw = torch.empty(N, enc.output_dim, device=dev), torch.empty(N, 1, device=dev)
+        st, p = ops._stream(), ops._ptr
+
+        def fused():
+            _lib.call("tgrid_density_fwd", C.byref(enc.desc), p(enc.embeddings), C.byref(co), p(t), S, N, C.byref(net.desc), p(net.params), p(dens_f), st)
+
+        def pair():
+            _lib.call("tgrid_encode_fwd", C.byref(enc.desc), p(enc.embeddings), C.byref(co), None, p(t), S, N, p(feat), st)
+            _lib.call("mlp_fwd", C.byref(net.desc), p(net.params), p(feat), enc.output_dim, N, p(raw), 1, 0, p(dens_p), st)
+
+        times = {"fused": [], "pair": []}
+        for rep in range(2 + 3 * args.rounds):
+            for name, fn in (("fused", fused), ("pair", pair)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                if rep >= 2:
+                    times[name].append(a.elapsed_time(b))
+        kernel[f"N=32768x{S}"] = {"fused_ms": {"median": statistics.median(times["fused"]), "min": min(times["fused"]), "max": max(times["fused"])},
+                                  "pair_ms": {"median": statistics.median(times["pair"]), "min": min(times["pair"]), "max": max(times["pair"])},
+                                  "bit_identical": bool(torch.equal(dens_f, dens_p))}
+
+    stat = lambda xs: {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "rounds": [round(x, 3) for x in xs]}
+    names = {"i": "eval_psnr: index table + trainer.forward(training=False) in 4096-ray slices (126 whole slices of the 126.6)",
+             "ii": "renderer, 32768-ray chunks, tgrid_encode_fwd + mlp_fwd per proposal level", "iii": "renderer, 32768-ray chunks, tgrid_density_fwd"}
+    res = {"what": f"960x540 frames of the stadium scene's evaluation cameras, nerfplayer-nerfacto preset ({args.mlp_operands} operands), R = 4096", "state": state,
+           "device": torch.cuda.get_device_name(0), "frames_per_arm_and_round": n_frames, "rounds": args.rounds, "anneal": anneal, "arms": {},
+           "arm_ii_and_iii_frames_bit_identical": same_bits, "kernel_groups_ms_per_frame_hip_events": groups, "density_kernel_alone": kernel,
+           "launch_count_note": "libsnerf launches per frame; arm i also issues ATen kernels per slice (the appearance mean, the random background, copies)"}
+    for k in arms:
+        s = stat(ms[k])
+        res["arms"][k] = {"arm": names[k], "ms_per_frame": s, "spread_ms": s["max"] - s["min"], "launches_per_frame": launches[k]}
+    ii, iii = res["arms"]["ii"]["ms_per_frame"], res["arms"]["iii"]["ms_per_frame"]
+    spread = max(ii["max"] - ii["min"], iii["max"] - iii["min"])
+    res["fused_density_default"] = {"iii_beats_ii_by_more_than_the_spread": bool(ii["median"] - iii["median"] > spread), "gain_ms": ii["median"] - iii["median"],
+                                    "spread_ms": spread}
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: {"ms_per_frame": round(v["ms_per_frame"]["median"], 2), "spread_ms": round(v["spread_ms"], 2), "launches": v["launches_per_frame"]}
+                      for k, v in res["arms"].items()}))
+    print(json.dumps({"kernel": kernel, "fused_density_default": res["fused_density_default"], "bit_identical_ii_iii": same_bits, "state": state}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--train-steps", type=int, default=5000)
+    ap.add_argument("--method", default="k-planes", choices=["k-planes", "nerfplayer-nerfacto"])
+    ap.add_argument("--train-steps", type=int, default=None, help="default: 5000 (k-planes), 0 (nerfplayer-nerfacto)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=6, help="frames per arm and round (novel cameras x times)")
-    ap.add_argument("--out", default="profiles/r09_render_bench.json")
+    ap.add_argument("--out", default=None, help="default: profiles/r09_render_bench.json (k-planes), profiles/r29_nerfplayer_render_bench.json")
+    ap.add_argument("--load-dir", default=None, help="nerfplayer-nerfacto: a checkpoint directory of the preset trained on the stadium scene (30 x 8 images)")
+    ap.add_argument("--mlp-operands", default="bf16", choices=["fp32", "bf16"], help="nerfplayer-nerfacto: NerfplayerTrainer(mlp_operands=...)")
     args = ap.parse_args()
+    if args.method == "nerfplayer-nerfacto":
+        args.train_steps = 0 if args.train_steps is None else args.train_steps
+        args.out = args.out or "profiles/r29_nerfplayer_render_bench.json"
+        return main_nerfplayer(args)
+    args.train_steps = 5000 if args.train_steps is None else args.train_steps
+    args.out = args.out or "profiles/r09_render_bench.json"
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     cfg = KPlanesTrainConfig(seed=0)

@@ -31,6 +31,17 @@ def eval_psnr(tr, data, n_images, anneal):
     return out_ps
 
 
+@torch.no_grad()
+def eval_psnr_renderer(rn, data, n_images, anneal):
+    """--renderer-eval: the same images through NerfplayerRenderer -- whole frames (the ragged last chunk included) on black, no per-slice work."""
+    from soccernerfs_amd.cameras import Cameras
+
+    imgs = data["images"]; M, H, W = imgs.shape[:3]
+    cams = Cameras(data["c2w"], data["fx"], data["fy"], data["cx"], data["cy"], W, H, data["times"])
+    ids = torch.linspace(0, M - 1, n_images).long().tolist()
+    return rn.evaluate(cams, imgs, ids, anneal=anneal)["psnr_per_image"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30000)
@@ -47,7 +58,13 @@ def main():
                     "from the HIP trainer's initial parameters): the reference-algorithm arm of config 4's PSNR comparison")
     ap.add_argument("--train-budget-s", type=float, default=0.0, help="stop training when this much wall-clock is spent (a gpurun call is capped at one hour), evaluate there")
     ap.add_argument("--tiled", action="store_true", help="NerfplayerTrainer(tiled_field_backward=True): the main table's scatter + TV + Adam as one owner-computes pass (round 6)")
+    ap.add_argument("--save-dir", default=None, help="write a nerfstudio checkpoint (NerfplayerTrainer.save_checkpoint) into this directory when training ends; "
+                    "tools/render.py --method nerfplayer-nerfacto --aabb-scale <1.0 for --scene stadium, else 1.5> renders it")
+    ap.add_argument("--renderer-eval", action="store_true", help="evaluate through soccernerfs_amd.render.NerfplayerRenderer (whole frames on black) instead of "
+                    "4096-ray slices through forward(training=False) with a random background")
     args = ap.parse_args()
+    if args.standin and (args.save_dir or args.renderer_eval):
+        ap.error("--save-dir and --renderer-eval belong to the fused trainer, not to --standin")
     dev = torch.device("cuda:0"); torch.manual_seed(args.seed)
     R = 4096
     Wd, Hd = args.width, args.width * 9 // 16
@@ -71,6 +88,12 @@ def main():
     log = {"config": f"nerfplayer-nerfacto preset, {'stock-PyTorch stand-in (oracle/nerfplayer_standin.py)' if args.standin else 'fused trainer'}, synthetic {'stadium-players scene' if stadium else 'clip'} ({M} training images {W}x{H}, "
                      f"{len(times)} frames per camera, 6 cameras held out), seed {args.seed}", "scene": args.scene, "mlp_operands": args.mlp_operands,
            "async_field_sweep": bool(args.async_sweep), "tiled_field_backward": bool(args.tiled), "standin": bool(args.standin), "evals": []}
+    renderer = None
+    if args.renderer_eval:
+        from soccernerfs_amd.render import NerfplayerRenderer
+
+        renderer = NerfplayerRenderer(tr)
+        log["eval"] = "NerfplayerRenderer: whole frames, black background"
     t_begin = time.time()
     t_train = 0.0
     for step in range(args.steps):
@@ -87,12 +110,19 @@ def main():
         if out_of_time:
             log["stopped_early_at_step"] = step + 1
         if (step + 1) % args.eval_every == 0 or step + 1 == args.steps or out_of_time:
-            ps = eval_psnr(tr, held, 6, anneal_value(step, 1000, 10.0))
-            ps_tr = eval_psnr(tr, train, 4, 1.0)
+            if renderer is not None:
+                ps = eval_psnr_renderer(renderer, held, 6, anneal_value(step, 1000, 10.0))
+                ps_tr = eval_psnr_renderer(renderer, train, 4, 1.0)
+            else:
+                ps = eval_psnr(tr, held, 6, anneal_value(step, 1000, 10.0))
+                ps_tr = eval_psnr(tr, train, 4, 1.0)
             log["evals"].append({"step": step + 1, "psnr_heldout_mean": sum(ps) / len(ps), "psnr_heldout": ps, "psnr_train_views_mean": sum(ps_tr) / len(ps_tr)})
             print(f"== step {step + 1}: held-out cameras PSNR {sum(ps) / len(ps):.2f} dB; train views {sum(ps_tr) / len(ps_tr):.2f} dB", flush=True)
         if out_of_time:
             break
+    if args.save_dir:
+        log["checkpoint"] = tr.save_checkpoint(args.save_dir)
+        print(f"checkpoint -> {log['checkpoint']}", flush=True)
     log["train_rays_per_s_mean"] = R * (log.get("stopped_early_at_step", args.steps) // 500 * 500) / max(t_train, 1e-9)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     json.dump(log, open(args.out, "w"), indent=1)
